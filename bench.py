@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the EchoGLAD GNN hot path on MI355X: echo frames/s through the full GNN stack.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path (3 fused GCN layers + the 4 classifier heads, eval mode,
@@ -14,9 +14,13 @@ independent units, so ranks shard the batch with no data-path collective (weak s
 this process touches the GPU; a failed rank makes the parent exit non-zero).  Under torch.distributed.run the
 environment's RANK / LOCAL_RANK / WORLD_SIZE are used as they are.
 
-Rank 0 prints ONE JSON line with `roofline` (dominant kernel, measured live with HIP events on
+A plain run sets up, warms up, times exactly K steps and has rank 0 print ONE JSON line: `metric`, `value` (frames/s),
+`ms_per_step` (milliseconds of one timed step), the configuration.  `--dump-outputs DIR` writes the logits of the last timed
+step as DIR/logits.npy (inputs and weights are seeded: the same arguments give the same inputs on every run).
+
+With `--full` the line also carries `roofline` (dominant kernel, measured live with HIP events on
 the launch stream), `cpu_baseline` (the CPU oracle = port of the reference PyG op sequence,
-timed on this box's host cores on a bounded sample), `repeats` (the timed loop repeated) and — at N = 1 —
+timed on the host cores on a bounded sample), `repeats` (the timed loop repeated) and — at N = 1 —
 `other_configs`: BASELINE configs[2] (main grid only, batch 32), configs[4] (448x448, 8 aux levels, batch 8) and one
 configs[3] training step (coordinate graph, batch 32), each timed the same way; they never enter `value`."""
 from __future__ import annotations
@@ -78,6 +82,14 @@ def parse():
     p.add_argument("--mode", choices=["infer", "train"], default="infer",
                    help="infer (default): BASELINE configs[1], the metric's configuration.  train: one full training "
                         "step of the GNN stack on configs[3] (coordinate graph; SURVEY 8d), reported under its own metric name")
+    p.add_argument("--full", action="store_true",
+                   help="measure and check everything beyond the headline as well: repeats, the eager step, the roofline, before / "
+                        "after the path, the CPU baseline and parity, the other configs, the shard digests and training leg at "
+                        "world > 1; in --mode train the roofline, the graph replay and the per-rank step times.  Without it a run "
+                        "sets up, warms up, times the K steps and prints the headline line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy "
+                        "(float32 / float64, at most 64 MB in all; rank 0)")
     return p.parse_args()
 
 
@@ -248,8 +260,31 @@ def train_workload(frame, naux, layers, B, device, world, rank, force_collective
         return engine.total_loss(engine.compute_loss(crit, preds, y, coord_preds, coord_y, valid, B))
 
     step.reducer = reducer
+    step.model = model
     step.graphed = (lambda warmup=2: engine.GraphedTrainStep(loss_fn, opt, warmup=warmup)) if capturable and reducer is None else None
     return step, topo
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays) -> None:
+    """--dump-outputs: one <path>/<name>.npy per array (float64 stays float64, everything else is written as float32).  If the
+    arrays together exceed DUMP_BYTES, each is cut to a fixed, seeded sample of its rows (sorted), written beside
+    <name>_rows.npy (float64 row indices), so that two builds run with the same arguments write comparable files."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: v if v.dtype == np.float64 else v.astype(np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BYTES and a.ndim > 0:
+            row_bytes = max(a.nbytes // max(a.shape[0], 1), 1)
+            keep = min(a.shape[0], int(DUMP_BYTES * a.nbytes / total) // (row_bytes + 8))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            np.save(os.path.join(path, f"{name}_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a))
 
 
 def logits_digest(t):
@@ -343,22 +378,27 @@ def main_train(args, world, rank, device, dist_info):
     if step.reducer is not None:
         step.reducer.profile = True                          # (events from here on: the measured steps)
     elapsed, loss = timed_loop(step, args.steps, world, device)
-    # per rank: its own clock over the same K steps (the reported time is the maximum), and how long its compute stream sat in
-    # finish() behind the gradient collectives -- what to look at first when the scaling curve bends
-    t0 = time.perf_counter()
-    torch.cuda.synchronize()
-    own = []
-    for _ in range(min(args.steps, 5)):
-        t0 = time.perf_counter()
-        step()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": loss.detach().reshape(1),
+                                         **{"param." + n: p for n, p in step.model.named_parameters()}})
+    # per rank (--full): its own clock over the same K steps (the reported time is the maximum), and how long its compute stream
+    # sat in finish() behind the gradient collectives -- what to look at first when the scaling curve bends
+    per_rank = None
+    if args.full:
         torch.cuda.synchronize()
-        own.append(1e3 * (time.perf_counter() - t0))
-    wait_ms = step.reducer.collective_wait_ms() if step.reducer is not None else None
-    per_rank = [{"rank": rank, "ms_per_step_alone": round(min(own), 3), "ms_in_finish_behind_collectives": None if wait_ms is None else round(wait_ms, 4)}]
-    if world > 1:
-        gathered = [None] * world
-        torch.distributed.all_gather_object(gathered, per_rank[0])
-        per_rank = gathered
+        own = []
+        for _ in range(min(args.steps, 5)):
+            t0 = time.perf_counter()
+            step()
+            torch.cuda.synchronize()
+            own.append(1e3 * (time.perf_counter() - t0))
+        wait_ms = step.reducer.collective_wait_ms() if step.reducer is not None else None
+        per_rank = [{"rank": rank, "ms_per_step_alone": round(min(own), 3),
+                     "ms_in_finish_behind_collectives": None if wait_ms is None else round(wait_ms, 4)}]
+        if world > 1:
+            gathered = [None] * world
+            torch.distributed.all_gather_object(gathered, per_rank[0])
+            per_rank = gathered
     if rank == 0:
         fps = world * B * args.steps / elapsed
         sb, sf = stack_work(topo, args.layers)
@@ -382,12 +422,15 @@ def main_train(args, world, rank, device, dist_info):
                                 note="ms_in_finish_behind_collectives = mean time per step the compute stream waited in "
                                      "GradientAllReducer.finish() for the bucket all-reduces (issued from inside backward on a "
                                      "side stream); ms_per_step_alone = this rank's own synchronised step time")}
-        if world == 1 and not args.no_other_configs:
+        if per_rank is None:
+            for k in ("per_rank", "note"):
+                del out["distributed"][k]
+        if args.full and world == 1 and not args.no_other_configs:
             try:
                 out["roofline"] = train_layer_roofline(B, topo, device, args.layers, step)
             except Exception as ex:
                 out["roofline"] = {"error": repr(ex)}
-        if world == 1 and step.reducer is None and not args.no_graph_replay:
+        if args.full and world == 1 and step.reducer is None and not args.no_graph_replay:
             del step
             import gc
             gc.collect()
@@ -927,11 +970,13 @@ def main_infer(args, world, rank, device, dist_info):
         out = step()
     elapsed, out = timed_loop(step, args.steps, world, device)          # THE timed region: exactly K steps
     frames_per_s = world * B * args.steps / elapsed
-    rep = [1e3 * timed_loop(step, args.steps, world, device)[0] / args.steps for _ in range(max(args.repeats, 0))]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"logits": out})
+    rep = [1e3 * timed_loop(step, args.steps, world, device)[0] / args.steps for _ in range(max(args.repeats, 0) if args.full else 0)]
     # the same step launched eagerly from Python (4 launches + queue resets per step), timed the same way: what a caller without
     # enable_hip_graph() gets
     eager_ms = None
-    if not args.no_hip_graph:
+    if args.full and not args.no_hip_graph:
         model.use_hip_graph = False                  # (the captured graph stays where it is)
         for _ in range(max(args.warmup, 3)):
             step()
@@ -941,7 +986,7 @@ def main_infer(args, world, rank, device, dist_info):
 
     # ---- every rank's logits for ITS shard must be what one GPU alone computes for the same frames (frames are seeded by global
     # rank index; the kernels are bitwise deterministic): rank 0 recomputes every other shard and compares digests
-    if world > 1:
+    if args.full and world > 1:
         digest = logits_digest(out)
         digests = [None] * world
         torch.distributed.all_gather_object(digests, digest)
@@ -961,7 +1006,7 @@ def main_infer(args, world, rank, device, dist_info):
                 print(f"warning: ranks {bad} computed other logits for their shard than rank 0 does for the same frames", file=sys.stderr)
     # ---- world > 1 (or --train-leg): the short training measurement every rank takes part in (the only collective of this framework)
     train_leg = None
-    if (args.train_leg or (world > 1 and not args.no_other_configs)) and args.frame == 224 and args.naux == 7 and not args.main_only \
+    if (args.train_leg or (args.full and world > 1 and not args.no_other_configs)) and args.frame == 224 and args.naux == 7 and not args.main_only \
             and os.environ.get("EG_BENCH_TRAIN_LEG", "1") != "0":
         try:
             train_leg = train_leg_all_ranks(args, world, rank, device)
@@ -969,8 +1014,37 @@ def main_infer(args, world, rank, device, dist_info):
             train_leg = {"error": repr(ex)}
     if rank != 0:
         return
-    # ---- dominant kernel: the fused GCN layer, timed with HIP events on the launch stream
     graph, gb = model._resolver.resolve(edge_index, feats.shape[0])
+    e_dir = 2 * topo.num_undirected_edges
+    stack_bytes, stack_flops = stack_work(topo, args.layers)
+    result = {
+        "metric": "echo frames/sec through full GNN stack (224x224 default hier-graph); MAE parity",
+        "value": round(frames_per_s, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"configs[1] default.yml: {args.frame}x{args.frame} frame, "
+                               f"{'main grid only' if args.main_only else str(args.naux) + ' aux levels'}, "
+                               f"num_gnn_layers={args.layers}, batch={B} per GPU, eval mode, "
+                               "node features [B*N,128] in HBM -> logits [B*N_valid,4] in HBM",
+                   "workload_short": f"configs[1] default.yml: {args.frame}x{args.frame}, "
+                                     f"{'main grid only' if args.main_only else str(args.naux) + ' aux levels'}, L={args.layers}, "
+                                     f"batch {B}/GPU, eval",
+                   "nodes_per_frame": N, "directed_edges_per_frame": e_dir, "global_batch": B * world,
+                   "parallelism": f"dp{world} (batch-sharded frames, no data-path collective)",
+                   "launch": "eager" if args.no_hip_graph else "hipGraph replay of the step's kernels",
+                   "kernels_per_step": ("2 x k_gcn_layer_ps<false> (chained layers) + k_gcn_layer_ps<true> (last layer + "
+                                        "classifier heads)") if (graph.kidsum_rows > 0 and model.chain_layers and
+                                                                  model.fuse_classifier) else "3 layer launches + k_classifier"},
+        "distributed": dist_info,
+        "stack_hbm_frac": round(frames_per_s / world * stack_bytes / 1e9 / PEAK_HBM_GBS, 4),
+        "stack_mfma_frac": round(frames_per_s / world * stack_flops / 1e12 / PEAK_F32_MFMA_TF, 4),
+    }
+    if not args.full:
+        if train_leg is not None:                             # (--train-leg asked for it)
+            result["other_configs"] = {f"cfg4_train_dp{world}": train_leg}
+        emit(result)
+        return
+    # ---- dominant kernel: the fused GCN layer, timed with HIP events on the launch stream
     w, scale, shift = model._folded_layers()[0]
     buf = torch.empty_like(feats)
     chained = bool(model.chain_layers and graph.kidsum_rows > 0 and args.layers > 1)
@@ -1029,7 +1103,6 @@ def main_infer(args, world, rank, device, dist_info):
         del bufs
     else:
         layer_ms = time_steps(layer_launches, iters=args.kernel_iters, warm=3) / len(forms)
-    e_dir = 2 * topo.num_undirected_edges
     flops = B * (N * 2 * C * C + (e_dir + N) * 2 * C)             # SURVEY §8(d) per-layer FLOPs
     bytes_alg = B * N * 2 * C * 4                                  # read x once + write out once
     tf = flops / (layer_ms * 1e-3) / 1e12
@@ -1047,34 +1120,13 @@ def main_infer(args, world, rank, device, dist_info):
                 "avg_launch_ms": round(layer_ms, 4), "avg_launch_timing": timing_note,
                 "hbm": {"achieved": round(gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
                         "frac": round(gbs / PEAK_HBM_GBS, 4), "algorithmic_bytes_per_launch": bytes_alg}}
-    stack_bytes, stack_flops = stack_work(topo, args.layers)
-    result = {
-        "metric": "echo frames/sec through full GNN stack (224x224 default hier-graph); MAE parity",
-        "value": round(frames_per_s, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 4),
-        "eager_ms_per_step": None if eager_ms is None else round(eager_ms, 4), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"configs[1] default.yml: {args.frame}x{args.frame} frame, "
-                               f"{'main grid only' if args.main_only else str(args.naux) + ' aux levels'}, "
-                               f"num_gnn_layers={args.layers}, batch={B} per GPU, eval mode, "
-                               "node features [B*N,128] in HBM -> logits [B*N_valid,4] in HBM",
-                   "workload_short": f"configs[1] default.yml: {args.frame}x{args.frame}, "
-                                     f"{'main grid only' if args.main_only else str(args.naux) + ' aux levels'}, L={args.layers}, "
-                                     f"batch {B}/GPU, eval",
-                   "nodes_per_frame": N, "directed_edges_per_frame": e_dir, "global_batch": B * world,
-                   "parallelism": f"dp{world} (batch-sharded frames, no data-path collective)",
-                   "launch": "eager" if args.no_hip_graph else "hipGraph replay of the step's kernels",
-                   "kernels_per_step": ("2 x k_gcn_layer_ps<false> (chained layers) + k_gcn_layer_ps<true> (last layer + "
-                                        "classifier heads)") if (graph.kidsum_rows > 0 and model.chain_layers and
-                                                                  model.fuse_classifier) else "3 layer launches + k_classifier"},
-        "distributed": dist_info,
+    result.update({
+        "eager_ms_per_step": None if eager_ms is None else round(eager_ms, 4),
         "repeats": ({"ms_per_step": {"min": round(min(rep), 4), "median": round(sorted(rep)[len(rep) // 2], 4),
                                      "max": round(max(rep), 4)}, "n": len(rep),
                      "note": "the K-step timed loop run again n times after the reported one"} if rep else None),
-        "stack_hbm_frac": round(frames_per_s / world * stack_bytes / 1e9 / PEAK_HBM_GBS, 4),
-        "stack_mfma_frac": round(frames_per_s / world * stack_flops / 1e12 / PEAK_F32_MFMA_TF, 4),
         "roofline": roofline,
-    }
+    })
     # ---- the rows right after the path, timed beside it; NOT part of `value`
     try:
         from echoglad_amd import evaluators as EV, losses as LS

@@ -56,7 +56,7 @@ def test_committed_pmc_summary_matches_the_committed_kernel_sources():
 
 @pytest.mark.gpu
 def test_bench_line_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "5", "--warmup", "2", "--no-cpu-baseline",
                         "--no-other-configs", "--repeats", "2", "--spinup", "0.05"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -75,6 +75,112 @@ def test_bench_line_contract():
     assert len(lines[0]) <= 1600 and os.path.exists(os.path.join(ROOT, d["details"]))
     full = json.load(open(os.path.join(ROOT, d["details"])))
     assert full["value"] == d["value"] and "avg_launch_timing" in full["roofline"]
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_times_k_steps_and_dumps_the_last_steps_logits(tmp_path):
+    """Without --full the run is lean: the headline keys only (no side measurement), `steps` timed steps, and --dump-outputs
+    writes the logits of the last timed step; the same arguments give the same inputs, so a second run writes the same bits."""
+    import numpy as np
+    got = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+            assert key in d, key
+        for key in ("roofline", "repeats", "eager_ms_per_step", "cpu_baseline", "parity", "other_configs", "after_path"):
+            assert key not in d, key
+        assert d["steps"] == 7 and d["warmup"] == 2 and d["unit"] == "frames/s" and d["dtype"] == "f32"
+        assert abs(d["value"] - 8 / (d["ms_per_step"] * 1e-3)) < 1e-2 * d["value"]
+        assert sorted(os.listdir(out)) == ["logits.npy"]
+        lg = np.load(out / "logits.npy")
+        assert lg.dtype == np.float32 and lg.shape == (8 * d["config"]["nodes_per_frame"], 4) and np.isfinite(lg).all()
+        got.append(lg)
+    assert np.array_equal(got[0], got[1])
+
+
+def _counting_clock(monkeypatch, b):
+    """bench's clock reads the number of steps taken so far: every step lasts exactly one second."""
+    import time
+    import types
+    import torch
+    calls = [0]
+    monkeypatch.setattr(b, "time", types.SimpleNamespace(perf_counter=lambda: float(calls[0]), time=time.time, sleep=time.sleep))
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+    lines = []
+    monkeypatch.setattr(b, "emit", lines.append)
+    return calls, lines
+
+
+@pytest.mark.parametrize("mode", ["infer", "train"])
+def test_plain_run_times_exactly_the_given_steps_and_dumps_the_last_one(tmp_path, monkeypatch, mode):
+    """The timed region spans exactly --steps steps (one second each here: ms_per_step is exactly 1000) and --dump-outputs writes
+    what the LAST timed step returned (each step returns its own number)."""
+    import types
+    import numpy as np
+    import torch
+    b = _bench()
+    calls, lines = _counting_clock(monkeypatch, b)
+    B, N, K, W = 2, 5, 7, 3
+    topo = types.SimpleNamespace(num_nodes=N, num_undirected_edges=3)
+
+    def step():
+        calls[0] += 1
+        return torch.full((B * N, 4), float(calls[0])) if mode == "infer" else torch.tensor(float(calls[0]))
+
+    if mode == "infer":
+        graph = types.SimpleNamespace(kidsum_rows=1)
+        model = types.SimpleNamespace(_resolver=types.SimpleNamespace(resolve=lambda ei, n: (graph, None)), chain_layers=True,
+                                      fuse_classifier=True)
+        monkeypatch.setattr(b, "infer_workload", lambda *a, **k: (model, {}, topo, torch.zeros(B * N, 128), None, step))
+        untimed = min(max(K + W, 32), 512) + W              # the launch burst in front of the warm-up steps, then the warm-up
+    else:
+        step.reducer, step.model = None, torch.nn.Linear(2, 2)
+        monkeypatch.setattr(b, "train_workload", lambda *a, **k: (step, topo))
+        untimed = W
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--mode", mode, "--batch", str(B), "--steps", str(K), "--warmup", str(W),
+                                      "--spinup", "0", "--dump-outputs", str(tmp_path)])
+    args = b.parse()
+    (b.main_infer if mode == "infer" else b.main_train)(args, 1, 0, "cpu", {"world_size": 1, "backend": None})
+    (d,) = lines
+    assert calls[0] == untimed + K                           # nothing runs after the timed steps without --full
+    assert d["steps"] == K and d["ms_per_step"] == 1000.0 and d["value"] == B
+    for key in ("roofline", "repeats", "eager_ms_per_step", "hip_graph_replay", "cpu_baseline", "other_configs"):
+        assert key not in d, key
+    if mode == "infer":
+        lg = np.load(tmp_path / "logits.npy")
+        assert lg.dtype == np.float32 and lg.shape == (B * N, 4) and (lg == untimed + K).all()
+    else:
+        assert np.load(tmp_path / "loss.npy").tolist() == [untimed + K]
+        assert sorted(os.listdir(tmp_path)) == ["loss.npy", "param.bias.npy", "param.weight.npy"]
+
+
+def test_dump_outputs_keeps_to_its_budget_with_a_fixed_sample(tmp_path, monkeypatch):
+    import numpy as np
+    b = _bench()
+    small = np.arange(12, dtype=np.float16).reshape(3, 4)
+    b.dump_outputs(str(tmp_path / "a"), {"x": small, "y": np.ones(2)})
+    assert sorted(os.listdir(tmp_path / "a")) == ["x.npy", "y.npy"]
+    x = np.load(tmp_path / "a" / "x.npy")
+    assert x.dtype == np.float32 and np.array_equal(x, small.astype(np.float32))
+    assert np.load(tmp_path / "a" / "y.npy").dtype == np.float64
+    monkeypatch.setattr(b, "DUMP_BYTES", 4096)
+    big = np.random.default_rng(1).standard_normal((1000, 4)).astype(np.float32)
+    for run in ("b", "c"):
+        b.dump_outputs(str(tmp_path / run), {"logits": big})
+    files = sorted(os.listdir(tmp_path / "b"))
+    assert files == ["logits.npy", "logits_rows.npy"]
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in files) <= 4096 + 2 * 128          # (+ the .npy headers)
+    rows = np.load(tmp_path / "b" / "logits_rows.npy")
+    assert rows.dtype == np.float64 and (np.diff(rows) > 0).all()
+    assert np.array_equal(np.load(tmp_path / "b" / "logits.npy"), big[rows.astype(np.int64)])
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f))
 
 
 def test_headline_of_a_full_result_fits_the_drivers_tail_window():

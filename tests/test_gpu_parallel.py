@@ -32,7 +32,7 @@ def test_reducer_hooks_on_rccl_world_1_leave_the_gradients_bit_identical():
 
 
 def test_bench_train_step_with_the_reducer_attached_on_one_gpu():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "train", "--batch", "4", "--steps", "3", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "train", "--full", "--batch", "4", "--steps", "3", "--warmup", "2",
                         "--force-collective", "--bucket-kb", "64"], capture_output=True, text=True, timeout=900, env=_child_env())
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -204,8 +204,8 @@ if __name__ == "__main__":
 
 
 def test_default_bench_takes_the_training_leg_on_every_rank():
-    """`bench.py --gpus N` (N > 1) is the inference headline -- no collective in it -- plus a short configs[3] training
-    measurement on ALL ranks, so that the driver's multi-GPU run of the default command also meets the gradient all-reduce.
+    """`bench.py --gpus N --full` (N > 1) is the inference headline -- no collective in it -- plus a short configs[3] training
+    measurement on ALL ranks, so that a multi-GPU run of the full command also meets the gradient all-reduce.
     `--train-leg` runs that code at world size 1 on a one-rank RCCL group: the line carries other_configs.cfg4_train_dp1 with
     both timings (collectives from inside backward / after it), the per-rank diagnostics and the collectives' sizes."""
     import json
@@ -235,7 +235,7 @@ def _world2_on_one_gpu(extra_env=None, extra_args=()):
     ranks itself (both on cuda:0; gloo reduces CUDA tensors through the host, RCCL refuses duplicate devices)."""
     env = _child_env()
     env.update(extra_env or {})
-    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-device",
+    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-device", "--full",
                            "--steps", "5", "--warmup", "2", "--repeats", "1", "--no-cpu-baseline", "--details", "inline", *extra_args],
                           capture_output=True, text=True, timeout=1200, env=env, cwd=ROOT)
 

@@ -1,12 +1,13 @@
 #!/bin/bash
 # Round profile: kernel-trace stats of the default bench command + separate PMC passes (HBM traffic counters).
 # usage (on the GPU box, from the repo root):  tools/profile_round.sh r01
-# Writes gpurun_out/profiles/<tag>_*.{csv,json,txt}; copy what should be judged into profiles/.
+# Writes $EG_OUT/profiles/<tag>_*.{csv,json,txt}; copy what should be judged into profiles/.
 TAG=${1:-r01}
-OUT=$PWD/gpurun_out/profiles
+EG_OUT=${EG_OUT:-tool_out}                 # results folder (the scripts that call each other share it)
+OUT=$EG_OUT/profiles
 mkdir -p $OUT
 export TMPDIR=/tmp
-CMD="bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-other-configs --repeats 0"
+CMD="bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-other-configs --repeats 0"
 cd $PWD
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$TAG/trace -- python3 $CMD > $OUT/${TAG}_trace_run.log 2>&1
 cp $(find /tmp/prof_$TAG/trace -name "*kernel_stats.csv" | head -1) $OUT/${TAG}_kernel_stats.csv 2>/dev/null

@@ -1,13 +1,14 @@
 #!/bin/bash
 # PMC passes over one training step (bench.py --mode train): per-kernel HBM bytes and MFMA-busy share, averaged per launch.
 # usage (GPU box, repo root):  bash tools/profile_train_pmc.sh r02 [batch]
-# Writes gpurun_out/profiles/<tag>_train_pmc.json; copy into profiles/ to have it judged.
+# Writes $EG_OUT/profiles/<tag>_train_pmc.json; copy into profiles/ to have it judged.
 TAG=${1:-r02}
 B=${2:-32}
-OUT=$PWD/gpurun_out/profiles
+EG_OUT=${EG_OUT:-tool_out}                 # results folder (the scripts that call each other share it)
+OUT=$EG_OUT/profiles
 mkdir -p $OUT
 export TMPDIR=/tmp
-CMD="bench.py --mode train --batch $B --steps 5 --warmup 2 --no-other-configs --no-graph-replay"   # STEPS below = 2 warm-up + 5 timed + 5 on the rank's own clock
+CMD="bench.py --mode train --full --batch $B --steps 5 --warmup 2 --no-other-configs --no-graph-replay"   # STEPS below = 2 warm-up + 5 timed + 5 on the rank's own clock
 rm -rf /tmp/prof_train_pmc
 for pmc in FETCH_SIZE WRITE_SIZE "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES" GRBM_GUI_ACTIVE; do
   n=$(echo $pmc | tr ' ' '_')
