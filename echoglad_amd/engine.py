@@ -189,9 +189,14 @@ def eval_step(model: Dict[str, torch.nn.Module], batch, criterion: Optional[Dict
 
 
 def update_evaluators(evaluators, preds, y, coord_preds, coord_y, pix2mm_x, pix2mm_y, valid, use_coordinate_graph):
-    """engine.py:466-492 without the `.detach().cpu()` of every tensor: the evaluators decode on the device."""
+    """engine.py:466-492 without the `.detach().cpu()` of every tensor: the evaluators decode / count on the device.  The
+    balanced accuracy takes (logits, labels, valid) -- the landmark logits also for coordinate-graph models, as engine.py:492
+    passes them; every other evaluator the landmark evaluator's five arguments."""
+    from .evaluators import BalancedBinaryAccuracyEvaluator
     for ev in evaluators.values():
-        if use_coordinate_graph:
+        if isinstance(ev, BalancedBinaryAccuracyEvaluator):
+            ev.update(preds, y, valid)
+        elif use_coordinate_graph:
             ev.update(coord_preds, coord_y, pix2mm_x, pix2mm_y, valid)
         else:
             ev.update(preds, y, pix2mm_x, pix2mm_y, valid)

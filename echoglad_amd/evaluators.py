@@ -1,10 +1,14 @@
-"""Landmark decode and width errors — host-side mirror of ``LandmarkExpectedCoordiantesEvaluator``
-(src/core/evaluators.py:237-617; the class name keeps the reference's spelling so a builder can swap it in) over
-the HIP decode kernel in csrc/heatmap.hip.
+"""The evaluators of the reference's engine (src/core/evaluators.py, src/builders/evaluator_builder.py) over HIP kernels.
 
-The reference moves the full logits to the host every step (engine.py:466-492) and evaluates the softmax heat map
-there.  Here the logits stay on the device: one kernel pass yields, per frame and landmark, the softmax-expected
-(h, w) over the last F*F rows, the label's (h, w) and the mean of ``valid``; only those [B,4,*] numbers are read back.
+``LandmarkExpectedCoordiantesEvaluator`` -- landmark decode and width errors, host-side mirror of evaluators.py:237-617 (the
+class name keeps the reference's spelling so a builder can swap it in) over the HIP decode kernel in csrc/heatmap.hip (SURVEY §8
+row f-3).  The reference moves the full logits to the host every step (engine.py:466-492) and evaluates the softmax heat map
+there.  Here the logits stay on the device: one kernel pass yields, per frame and landmark, the softmax-expected (h, w) over the
+last F*F rows, the label's (h, w) and the mean of ``valid``; only those [B,4,*] numbers are read back.
+
+``BalancedBinaryAccuracyEvaluator`` -- the default config's ``eval.standard`` (evaluators.py:85-143).  The reference runs four
+sklearn calls on host copies of the logits, labels and valid every update; here one launch (csrc/metrics.hip) appends the
+per-channel confusion counts to a device-side history, and the scores are formed from the counts on the host when read.
 """
 from __future__ import annotations
 
@@ -144,3 +148,123 @@ class LandmarkExpectedCoordiantesEvaluator(object):
 
 
 LandmarkExpectedCoordinatesEvaluator = LandmarkExpectedCoordiantesEvaluator
+
+
+def balanced_accuracy_from_counts(counts) -> np.ndarray:
+    """[..., C, 4] confusion counts {TP, FN, FP, TN} -> [..., C] float64 balanced accuracies with sklearn's arithmetic
+    (sklearn.metrics.balanced_accuracy_score, adjusted=False): recall = diag / row sum of every class that has support among
+    the valid rows (a class present only in the predictions is 0/0 and dropped), the score is the mean of those recalls; a
+    channel without a valid row scores 0 (evaluators.py:137-141)."""
+    c = np.asarray(counts, dtype=np.int64)
+    if c.ndim < 2 or c.shape[-1] != 4:
+        raise ValueError(f"counts must be [..., C, 4], got {c.shape}")
+    tp, fn, fp, tn = c[..., 0], c[..., 1], c[..., 2], c[..., 3]
+    neg, pos = tn + fp, tp + fn                              # row sums of the confusion matrix: support of class 0, class 1
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r0 = tn / neg                                        # recall of class 0 (sorted first, as sklearn's labels are)
+        r1 = tp / pos
+    # np.mean of [r0, r1] is (0 + r0 + r1) / 2, of [r] is r / 1: the same bits as the expressions below
+    both = (r0 + r1) / 2
+    return np.where((neg > 0) & (pos > 0), both, np.where(neg > 0, r0, np.where(pos > 0, r1, 0.0))).astype(np.float64)
+
+
+class BalancedBinaryAccuracyEvaluator(object):
+    """Same constructor, methods and numbers as the reference class (evaluators.py:85-143), over device-side counting.
+
+    ``update(y_pred, y_true, valid)`` takes CUDA tensors [rows, C] (float32, contiguous; 1 <= C <= 8) and appends one record of
+    confusion counts per call with ONE kernel launch: it neither synchronises nor allocates, so it can be captured into a HIP
+    graph (every replay appends a record).  The history holds ``max_updates`` records, sized once (at construction on the current
+    CUDA device for ``channels`` channels; an update on another device or with another channel count re-sizes it only while
+    nothing has been recorded).  Past ``max_updates`` the records are dropped and reading the scores raises.
+    ``score_per_class`` (None before the first update, else [N, C] float64) is read back from the device when accessed."""
+
+    def __init__(self, logger, max_updates: int = 65536, channels: int = 4):
+        if max_updates < 1:
+            raise ValueError("max_updates must be >= 1")
+        self.max_updates = int(max_updates)
+        self._state = None               # (device, channels, history [max_updates, C, 4] i64, counter [1] i64, workspace u8)
+        self._launched = 0               # update() calls since the state was allocated or reset (host side)
+        if torch.cuda.is_available():
+            self._allocate(torch.device("cuda", torch.cuda.current_device()), channels)
+
+    def _allocate(self, device, channels):
+        history = torch.zeros(self.max_updates, channels, 4, dtype=torch.int64, device=device)
+        counter = torch.zeros(1, dtype=torch.int64, device=device)
+        workspace = torch.empty(ops.CONFUSION_WORKSPACE_BYTES, dtype=torch.uint8, device=device)
+        self._state = (device, channels, history, counter, workspace)
+        self._launched = 0
+
+    def reset(self):
+        if self._state is not None:
+            self._state[3].zero_()
+        self._launched = 0
+
+    def update(self, y_pred, y_true, valid):
+        """evaluators.py:100-117.  y_pred: the model's output [rows, C] (threshold: > 0.5 on it as it is); y_true: {0, 1} labels."""
+        ch = y_pred.shape[-1]
+        pred, y, v = (t.detach().reshape(-1, ch) for t in (y_pred, y_true, valid))
+        st = self._state
+        if st is None or st[0] != pred.device or st[1] != ch:
+            if not pred.is_cuda:
+                raise RuntimeError("y_pred must be a CUDA (ROCm) tensor: the HIP path has no CPU fallback")
+            if st is not None and self._launched:
+                raise RuntimeError(f"this evaluator records {st[1]} channels on {st[0]}: got {ch} on {pred.device} (reset() first)")
+            self._allocate(pred.device, ch)
+            st = self._state
+        ops.confusion_counts(pred, y, v, st[2], st[3], st[4])
+        self._launched += 1
+
+    def counts(self):
+        """[N, C, 4] int64 numpy array of the recorded {TP, FN, FP, TN} (host read-back; None before the first update)."""
+        if self._state is None:
+            return None
+        history, counter = self._state[2], self._state[3]
+        n = int(counter.item())
+        if n > self.max_updates:
+            raise RuntimeError(f"{n} updates since the last reset() but the history holds max_updates = {self.max_updates}: "
+                               "construct the evaluator with a larger max_updates")
+        if n == 0:
+            return None
+        return history[:n].cpu().numpy()
+
+    @property
+    def score_per_class(self):
+        c = self.counts()
+        return None if c is None else balanced_accuracy_from_counts(c)
+
+    def compute(self):
+        """evaluators.py:119-124."""
+        return self.score_per_class.mean(axis=0).mean()
+
+    def get_per_class_score(self):
+        return self.score_per_class.mean(axis=0)
+
+    def get_last(self):
+        return self.score_per_class[-1, :].mean()
+
+
+_UNREACHABLE = ("accuracy", "mse", "landmarkerror")
+
+
+def build(eval_config, logger=None):
+    """src/builders/evaluator_builder.py: {standard: evaluator} for ``eval_config['standards']``.  The keys ``batch_size``,
+    ``frame_size`` and ``use_coordinate_graph`` configure the landmark evaluator."""
+    standards = list(eval_config["standards"])
+    batch_size, frame_size = eval_config["batch_size"], eval_config["frame_size"]
+    use_coord_graph = eval_config["use_coordinate_graph"]
+    evaluators = {}
+    for standard in standards:
+        if standard == "balancedaccuracy":
+            evaluators[standard] = BalancedBinaryAccuracyEvaluator(logger=logger)
+        elif standard == "landmarkcoorderror":
+            evaluators[standard] = LandmarkExpectedCoordiantesEvaluator(logger=logger, batch_size=batch_size,
+                                                                        frame_size=frame_size, use_coord_graph=use_coord_graph)
+        elif standard in _UNREACHABLE:
+            raise NotImplementedError(f"evaluator {standard!r} is not implemented: its update(y_pred, y_true) takes two arguments and "
+                                      "the reference's engine calls every evaluator with three or five (src/engine.py:492), so the "
+                                      "reference cannot run it either")
+        else:
+            raise KeyError(f"unknown evaluation standard {standard!r}")
+        if logger is not None and hasattr(logger, "infov"):
+            logger.infov("{} evaluator is built.".format(standard.upper()))
+    return evaluators

@@ -1029,6 +1029,41 @@ def bce_logits(logits, labels, valid=None, ones_weight: float = 1.0) -> torch.Te
     return _BCELogitsFn.apply(logits, labels, valid, float(ones_weight))
 
 
+CONFUSION_MAX_CHANNELS = 8
+CONFUSION_WORKSPACE_BYTES = 512 * CONFUSION_MAX_CHANNELS * 32      # the full grid of eg_confusion_counts at any channel count
+
+
+def confusion_counts(pred: torch.Tensor, y: torch.Tensor, valid: torch.Tensor, history: torch.Tensor, counter: torch.Tensor,
+                     workspace: torch.Tensor) -> None:
+    """Append one record of per-channel confusion counts {TP, FN, FP, TN} over the rows with valid > 0 (prediction positive iff
+    pred > 0.5, label positive iff y != 0) to ``history[counter]`` and advance ``counter`` -- ONE launch on the current stream, no
+    host synchronisation, no allocation.  pred / y / valid: contiguous CUDA float32 [rows, C], 1 <= C <= 8; history: int64
+    [capacity, C, 4]; counter: int64 [1]; workspace: CONFUSION_WORKSPACE_BYTES bytes, not shared with another stream's launch.
+    Past capacity nothing is written but the counter still advances."""
+    for name, t in (("pred", pred), ("y", y), ("valid", valid), ("history", history), ("counter", counter), ("workspace", workspace)):
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} must be a CUDA (ROCm) tensor: the HIP path has no CPU fallback")
+        if t.device != pred.device:
+            raise RuntimeError(f"{name} is on {t.device}, pred on {pred.device}")
+        if not t.is_contiguous():
+            raise RuntimeError(f"{name} must be contiguous")
+    if pred.dim() != 2 or not 1 <= pred.shape[1] <= CONFUSION_MAX_CHANNELS or pred.shape[0] < 1:
+        raise RuntimeError(f"pred must be [rows >= 1, 1..{CONFUSION_MAX_CHANNELS}], got {tuple(pred.shape)}")
+    rows, ch = pred.shape
+    for name, t in (("pred", pred), ("y", y), ("valid", valid)):
+        if t.dtype != torch.float32 or t.shape != pred.shape:
+            raise RuntimeError(f"{name} must be float32 {tuple(pred.shape)}, got {tuple(t.shape)} {t.dtype}")
+    if history.dtype != torch.int64 or history.dim() != 3 or history.shape[1:] != (ch, 4) or history.shape[0] < 1:
+        raise RuntimeError(f"history must be int64 [capacity, {ch}, 4], got {tuple(history.shape)} {history.dtype}")
+    if counter.dtype != torch.int64 or counter.numel() != 1:
+        raise RuntimeError("counter must be one int64 element")
+    if workspace.dtype != torch.uint8 or workspace.numel() < CONFUSION_WORKSPACE_BYTES:
+        raise RuntimeError(f"workspace must be uint8 with at least {CONFUSION_WORKSPACE_BYTES} bytes")
+    stream = _stream(pred)
+    _lib.check(_lib.load().eg_confusion_counts(_ptr(pred), _ptr(y), _ptr(valid), rows, ch, _ptr(workspace), workspace.numel(),
+                                               _ptr(history), history.shape[0], _ptr(counter), stream), "eg_confusion_counts")
+
+
 class _CriteriaFn(torch.autograd.Function):
     """WeightedBCEWithLogitsLoss + ExpectedLandmarkMSE (+ MSE on the landmark coordinates) of one training step as ONE autograd
     node over eg_criteria_fwd / eg_criteria_bwd: (logits [B*n,4], coord_pred [R,2] | None) -> (total, bce, elm, coord | None),

@@ -84,8 +84,9 @@ extern "C" {
  * 132: eg_classifier_bwd_sums, eg_gcn_layer_bwd_presummed.  133: eg_graph_layer_launches, eg_debug_layer_timing_*, eg_elm_reduce, eg_coord_mlp_*_rows, eg_bilinear4_*_rows (round 5).
  * 134: eg_dropout_epoch_add / _set, eg_debug_dropout_epoch (round 5: a whole train step as one HIP graph).
  * 135: eg_gcn_layer_bwd_lower, eg_bilinear4_bwd_rows_sums, eg_avg_pool_pyramid_fwd / _bwd, eg_criteria_* (round 6).
- * 136: eg_classifier_train_fwd_act(h_sparse), eg_classifier_bwd_sums(layer_residual, recompute_h).  137, 138: eg_coord_update_fwd / _bwd.  139, 140: eg_adam_step. */
-#define EG_ABI_VERSION 140
+ * 136: eg_classifier_train_fwd_act(h_sparse), eg_classifier_bwd_sums(layer_residual, recompute_h).  137, 138: eg_coord_update_fwd / _bwd.  139, 140: eg_adam_step.
+ * 141: eg_confusion_counts. */
+#define EG_ABI_VERSION 141
 
 #define EG_CHANNELS 128 /* node_embedding_dim == node_hidden_dim (configs/default.yml:13-14) */
 
@@ -572,6 +573,20 @@ int eg_criteria_bwd(const float* logits, const float* labels, const float* valid
                     const float* d_expect, const float* bce_scale, const float* d_coord, int64_t n_coord, const float* g_total,
                     const float* g_bce, const float* g_elm, const float* g_coord, float* d_logits, float* d_coord_out,
                     eg_stream_t stream);
+
+/* ---- confusion counts of the landmark classifier (reference: BalancedBinaryAccuracyEvaluator, src/core/evaluators.py:85-143) --
+ * pred, y, valid: [rows, channels] f32 (1 <= channels <= 8, rows >= 1).  For every channel c, over the rows with valid > 0:
+ *   TP = #(y != 0 and pred > 0.5), FN = #(y != 0 and not pred > 0.5), FP = #(y == 0 and pred > 0.5), TN = #(y == 0 and not pred > 0.5)
+ * (a strict > 0.5 on whatever the model returned; a NaN prediction is a negative one).  ONE launch, integer counts, exact and
+ * bit-reproducible.  Writes the record history[k][c][0..3] = {TP, FN, FP, TN} (int64, history: [capacity][channels][4]) where
+ * k = *counter, a device int64 the launch then advances by one: a launch captured into a HIP graph appends one record per replay.
+ * With k >= capacity nothing is written but *counter still advances (the reader detects the overflow).  workspace: device memory of
+ * workspace_bytes bytes (8-byte aligned) for the per-workgroup partials, 512 * channels * 32 bytes for the full grid (less gives
+ * fewer workgroups); it must not be shared with a launch in flight on another stream.  The completion ticket is a word per
+ * (device, stream) allocated at the first launch on a stream: make that first launch outside a stream capture.
+ * EG_ERR_UNSUPPORTED for channels outside 1..8, EG_ERR_ARG for a NULL buffer or misaligned 64-bit buffer; nothing launched then. */
+int eg_confusion_counts(const float* pred, const float* y, const float* valid, int64_t rows, int channels, void* workspace,
+                        size_t workspace_bytes, int64_t* history, int64_t capacity, int64_t* counter, eg_stream_t stream);
 
 /* ---- node-feature packing (the step right before the hot path) -------------------------------------------
  * Reference: the per-sample loops at the tail of create_node_pixels (src/core/models.py:498-537, :590-636,
