@@ -115,10 +115,35 @@ __device__ inline void wave_gtmax4(float (&g)[4], int (&gh)[4], int (&gw)[4]) {
 
 __device__ inline float bce_logits(float x, float y) { return fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x))); }
 
+// nn.BCELoss on probabilities (criterion.py:6-27, WeightedBCE) with torch's own element formula and gradient:
+//   loss = (y - 1) max(log1p(-p), -100) - y max(log p, -100),   d loss / d p = (p - y) / max((1 - p) p, 1e-12).
+// torch raises for p outside [0, 1]; a kernel that may sit inside a captured graph cannot, so such an element (NaN included) gives a
+// NaN loss and a NaN gradient -- and NaN reaches the reduced loss, whether that element is valid or not (NaN * 0 = NaN), as torch's
+// check does not look at `valid` either.
+__device__ inline float bce_probs(float p, float y) {
+    const float l = (y - 1.0f) * fmaxf(log1pf(-p), -100.0f) - y * fmaxf(logf(p), -100.0f);
+    return (p >= 0.0f && p <= 1.0f) ? l : __builtin_nanf("");
+}
+__device__ inline float bce_probs_grad(float p, float y) {
+    const float g = (p - y) / fmaxf((1.0f - p) * p, 1e-12f);
+    return (p >= 0.0f && p <= 1.0f) ? g : __builtin_nanf("");
+}
+// which BCE a pass computes: none, with logits (WeightedBCEWithLogitsLoss), on probabilities (WeightedBCE)
+enum { BCE_NONE = 0, BCE_LOGITS = 1, BCE_PROBS = 2 };
+template <int MODE>
+__device__ inline float bce_elem(float x, float y) { return MODE == BCE_PROBS ? bce_probs(x, y) : bce_logits(x, y); }
+// d bce / d x before the weight: sigmoid(x) - y with logits
+template <int MODE>
+__device__ inline float bce_elem_grad(float x, float y) {
+    if (MODE == BCE_PROBS) return bce_probs_grad(x, y);
+    const float sg = 1.0f / (1.0f + expf(-x));
+    return sg - y;
+}
+
 // BCE: the levels tile the frame's rows (the training step's criteria: eg_criteria_fwd checks it), so this pass sees every logit, label
 // and valid flag once anyway -- the weighted BCE's partial sums (k_bce_partial's arithmetic per element) come out of it as well, one
 // (sum, sum valid) pair per workgroup at bce_part[2 * blockIdx.x]: no pass of its own over the same three arrays.
-template <bool BCE>
+template <int BCE>
 __global__ __launch_bounds__(HM_THREADS) void k_hm_partial(const float* __restrict__ logits, const float* __restrict__ y,
                                                            const float* __restrict__ valid, double* __restrict__ part,
                                                            const HmLevels L, float ones_weight, double* __restrict__ bce_part) {
@@ -179,7 +204,7 @@ __global__ __launch_bounds__(HM_THREADS) void k_hm_partial(const float* __restri
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 const float wgt = (ones_weight > 1.0f && tv[c] == 1.0f) ? ones_weight : 1.0f;
-                bce_a += (double)(wgt * bce_logits(xv[c], tv[c])) * va[c];
+                bce_a += (double)(wgt * bce_elem<BCE>(xv[c], tv[c])) * va[c];
                 bce_v += va[c];
             }
         }
@@ -338,7 +363,9 @@ constexpr int BCE_BLOCKS = 2048;
 
 // 16 B per operand and lane, two float4 groups in flight per stream (one element per lane and iteration made the pass a chain
 // of dependent memory round trips: 84 us for 110 MB at batch 32); n4 = n / 4 whole groups, the last n % 4 elements by lane 0 of
-// the last workgroup.  fp64 sums per lane, fixed tree per workgroup, fixed order over workgroups (k_bce_final).
+// the last workgroup.  fp64 sums per lane, fixed tree per workgroup, fixed order over workgroups (k_bce_final).  MODE: BCE_LOGITS
+// or BCE_PROBS.
+template <int MODE>
 __global__ __launch_bounds__(HM_THREADS) void k_bce_partial(const float* __restrict__ x, const float* __restrict__ y,
                                                             const float* __restrict__ valid, long long n, float ones_weight,
                                                             double* __restrict__ part) {
@@ -347,7 +374,7 @@ __global__ __launch_bounds__(HM_THREADS) void k_bce_partial(const float* __restr
     double a = 0, v = 0;
     auto one = [&](float xi, float yi, float vi) {
         const float w = (ones_weight > 1.0f && yi == 1.0f) ? ones_weight : 1.0f;
-        a += (double)(w * bce_logits(xi, yi)) * vi;
+        a += (double)(w * bce_elem<MODE>(xi, yi)) * vi;
         v += vi;
     };
     const long long n4 = n >> 2, stride = (long long)gridDim.x * HM_THREADS;
@@ -379,6 +406,7 @@ __global__ __launch_bounds__(64) void k_bce_final(const double* __restrict__ par
     if (l == 0) { out[0] = (float)a; out[1] = (float)v; out[2] = (float)(a / v); }
 }
 
+template <int MODE>
 __global__ __launch_bounds__(HM_THREADS) void k_bce_bwd(const float* __restrict__ x, const float* __restrict__ y,
                                                         const float* __restrict__ valid, long long n, float ones_weight,
                                                         const float* __restrict__ scale, float* __restrict__ dx) {
@@ -386,8 +414,7 @@ __global__ __launch_bounds__(HM_THREADS) void k_bce_bwd(const float* __restrict_
     if (i >= n) return;
     const float yi = y[i], vi = valid ? valid[i] : 1.0f;
     const float w = (ones_weight > 1.0f && yi == 1.0f) ? ones_weight : 1.0f;
-    const float sg = 1.0f / (1.0f + expf(-x[i]));
-    dx[i] = (sg - yi) * w * vi * scale[0];
+    dx[i] = bce_elem_grad<MODE>(x[i], yi) * w * vi * scale[0];
 }
 
 static int fill_levels(int batch, int64_t n_rows, const int* level_start, const int* level_side, int n_levels, HmLevels& L) {
@@ -442,8 +469,10 @@ __global__ __launch_bounds__(128) void k_elm_reduce(const float* __restrict__ ex
 }
 
 
-// ---- the three criteria of a training step as ONE node (engine.py:582-600 + criterion.py:13-27, :36-48, :93-151) -----------------
-// forward: k_bce_partial + k_hm_partial + k_hm_final + k_criteria_final (4 launches); backward: k_criteria_bwd (1 launch).  As
+// ---- the three criteria of a training step as ONE node (engine.py:582-600 + criterion.py:6-33, :36-63, :93-151) -----------------
+// forward: k_bce_partial + k_hm_partial + k_hm_final + k_criteria_final (4 launches); backward: k_criteria_bwd (1 launch).  The BCE is
+// with logits (WeightedBCEWithLogitsLoss) or on probabilities (WeightedBCE: a template argument of the passes that see the elements),
+// the coordinate criterion MSE or MAE (a flag of the final step, which also writes its gradient) -- same launches either way.  As
 // separate autograd nodes with torch's glue around them the same arithmetic was ~33 launches of ~5 us each -- a sixth of a
 // batch-1 training step captured into a HIP graph.
 struct CriteriaFinal {
@@ -457,9 +486,10 @@ struct CriteriaFinal {
     const float *coord_pred, *coord_y;      // nullable: no coordinate criterion
     int n_coord;
     float w_coord;
-    float* d_coord;                         // [n_coord] = w_coord * 2 (pred - y) / n_coord
+    float* d_coord;                         // [n_coord] = w_coord * 2 (pred - y) / n_coord (MSE; MAE: below)
     float *total, *bce, *elm, *coord;       // one float each
     float* bce_scale;                       // w_bce / sum(valid): what every element of the BCE gradient is multiplied by
+    int coord_l1;                           // coordinate criterion: 0 MSE, 1 MAE (mean |pred - y|, d_coord = w_coord sign(pred - y) / n)
 };
 
 // (the first 128 threads of the workgroup work; every thread of it must come here: one barrier)
@@ -526,9 +556,17 @@ __device__ inline void criteria_final_body(const CriteriaFinal& a) {
     }
     s_bce[0][t] = ba;
     s_bce[1][t] = bv;
-    // coordinate MSE (mean over all elements) and its gradient
+    // coordinate MSE or MAE (mean over all elements) and its gradient
     double cs = 0.0;
-    if (a.coord_pred) {
+    if (a.coord_pred && a.coord_l1) {
+        // torch's l1_loss backward: sgn(d) * (w / n), sgn(0) = 0
+        const float g = a.w_coord / (float)a.n_coord;
+        for (int i = t; i < a.n_coord; i += 128) {
+            const float d = a.coord_pred[i] - a.coord_y[i];
+            cs += (double)fabsf(d);
+            a.d_coord[i] = d > 0.f ? g : (d < 0.f ? -g : 0.f);
+        }
+    } else if (a.coord_pred) {
         const float inv_n = 1.0f / (float)a.n_coord;
         for (int i = t; i < a.n_coord; i += 128) {
             const float d = a.coord_pred[i] - a.coord_y[i];
@@ -573,6 +611,7 @@ struct CriteriaBwd {
     float* d_coord_out;                      // nullable
 };
 
+template <int MODE>
 __global__ __launch_bounds__(HM_THREADS) void k_criteria_bwd(const CriteriaBwd a, const HmLevels L) {
     const float gt = a.g_total ? *a.g_total : 0.f;
     const float s_bce = (gt + (a.g_bce ? *a.g_bce : 0.f)) * a.bce_scale[0];
@@ -591,8 +630,7 @@ __global__ __launch_bounds__(HM_THREADS) void k_criteria_bwd(const CriteriaBwd a
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         const float w = (a.ones_weight > 1.0f && yv[c] == 1.0f) ? a.ones_weight : 1.0f;
-        const float sg = 1.0f / (1.0f + expf(-xv[c]));
-        o[c] = (sg - yv[c]) * w * vv[c] * s_bce;
+        o[c] = bce_elem_grad<MODE>(xv[c], yv[c]) * w * vv[c] * s_bce;
     }
     if (l >= 0) {
         const int rr = r - L.start[l], side = L.side[l];
@@ -631,7 +669,7 @@ int eg_heatmap_expect_fwd(const float* logits, const float* labels, const float*
     int rc = fill_levels(batch, n_rows, level_start, level_side, n_levels, L);
     if (rc != EG_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_hm_partial<false>, dim3((unsigned)(batch * L.total_chunks)), dim3(HM_THREADS), 0, s, logits,
+    hipLaunchKernelGGL(k_hm_partial<BCE_NONE>, dim3((unsigned)(batch * L.total_chunks)), dim3(HM_THREADS), 0, s, logits,
                        gt ? labels : nullptr, vmean ? valid : nullptr, (double*)workspace, L, 0.f, (double*)nullptr);
     const int n_out = batch * n_levels * 4;
     hipLaunchKernelGGL(k_hm_final, dim3((unsigned)((n_out + 3) / 4)), dim3(256), 0, s, (const double*)workspace, expect,
@@ -654,28 +692,54 @@ int eg_heatmap_expect_bwd(const float* logits, const float* expect, const float*
     return EG_OK;
 }
 
-int eg_bce_logits_fwd(const float* logits, const float* labels, const float* valid, int64_t n, float ones_weight,
-                      void* workspace, float* out3, eg_stream_t stream) {
-    if (!logits || !labels || !workspace || !out3 || n < 1) return set_error(EG_ERR_ARG, "bad argument");
-    if (((uintptr_t)logits | (uintptr_t)labels | (uintptr_t)valid) & 15) return set_error(EG_ERR_ARG, "logits / labels / valid must be 16-byte aligned");
+}  // extern "C"
+
+template <int MODE>
+static int bce_fwd(const float* x, const float* labels, const float* valid, int64_t n, float ones_weight, void* workspace, float* out3,
+                   eg_stream_t stream) {
+    if (!x || !labels || !workspace || !out3 || n < 1) return set_error(EG_ERR_ARG, "bad argument");
+    if (((uintptr_t)x | (uintptr_t)labels | (uintptr_t)valid) & 15) return set_error(EG_ERR_ARG, "logits / labels / valid must be 16-byte aligned");
     long long blocks = ((n >> 2) + 2 * HM_THREADS - 1) / (2 * HM_THREADS);
     if (blocks < 1) blocks = 1;
     if (blocks > BCE_BLOCKS) blocks = BCE_BLOCKS;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_bce_partial, dim3((unsigned)blocks), dim3(HM_THREADS), 0, s, logits, labels, valid, (long long)n,
+    hipLaunchKernelGGL(k_bce_partial<MODE>, dim3((unsigned)blocks), dim3(HM_THREADS), 0, s, x, labels, valid, (long long)n,
                        ones_weight, (double*)workspace);
     hipLaunchKernelGGL(k_bce_final, dim3(1), dim3(64), 0, s, (const double*)workspace, (int)blocks, out3);
     EG_HIP_TRY(hipGetLastError());
     return EG_OK;
 }
 
-int eg_bce_logits_bwd(const float* logits, const float* labels, const float* valid, int64_t n, float ones_weight,
-                      const float* scale_dev, float* d_logits, eg_stream_t stream) {
-    if (!logits || !labels || !scale_dev || !d_logits || n < 1) return set_error(EG_ERR_ARG, "bad argument");
-    hipLaunchKernelGGL(k_bce_bwd, dim3((unsigned)((n + HM_THREADS - 1) / HM_THREADS)), dim3(HM_THREADS), 0, (hipStream_t)stream,
-                       logits, labels, valid, (long long)n, ones_weight, scale_dev, d_logits);
+template <int MODE>
+static int bce_bwd(const float* x, const float* labels, const float* valid, int64_t n, float ones_weight, const float* scale_dev,
+                   float* dx, eg_stream_t stream) {
+    if (!x || !labels || !scale_dev || !dx || n < 1) return set_error(EG_ERR_ARG, "bad argument");
+    hipLaunchKernelGGL(k_bce_bwd<MODE>, dim3((unsigned)((n + HM_THREADS - 1) / HM_THREADS)), dim3(HM_THREADS), 0, (hipStream_t)stream,
+                       x, labels, valid, (long long)n, ones_weight, scale_dev, dx);
     EG_HIP_TRY(hipGetLastError());
     return EG_OK;
+}
+
+extern "C" {
+
+int eg_bce_logits_fwd(const float* logits, const float* labels, const float* valid, int64_t n, float ones_weight,
+                      void* workspace, float* out3, eg_stream_t stream) {
+    return bce_fwd<BCE_LOGITS>(logits, labels, valid, n, ones_weight, workspace, out3, stream);
+}
+
+int eg_bce_logits_bwd(const float* logits, const float* labels, const float* valid, int64_t n, float ones_weight,
+                      const float* scale_dev, float* d_logits, eg_stream_t stream) {
+    return bce_bwd<BCE_LOGITS>(logits, labels, valid, n, ones_weight, scale_dev, d_logits, stream);
+}
+
+int eg_bce_probs_fwd(const float* probs, const float* labels, const float* valid, int64_t n, float ones_weight,
+                     void* workspace, float* out3, eg_stream_t stream) {
+    return bce_fwd<BCE_PROBS>(probs, labels, valid, n, ones_weight, workspace, out3, stream);
+}
+
+int eg_bce_probs_bwd(const float* probs, const float* labels, const float* valid, int64_t n, float ones_weight,
+                     const float* scale_dev, float* d_probs, eg_stream_t stream) {
+    return bce_bwd<BCE_PROBS>(probs, labels, valid, n, ones_weight, scale_dev, d_probs, stream);
 }
 
 int eg_elm_reduce(const float* expect, const float* gt, const float* vmean, const float* inv_side, int batch, int n_levels, float weight,
@@ -701,11 +765,12 @@ size_t eg_criteria_workspace_bytes(int batch, const int* level_side, int n_level
            (size_t)batch * n_levels * 12 * sizeof(float);           // + gt [B,L,4,2] and vmean [B,L,4]
 }
 
-int eg_criteria_fwd(const float* logits, const float* labels, const float* valid, int batch, int64_t n_rows, const int* level_start,
-                    const int* level_side, int n_levels, const float* inv_side, float bce_ones_weight, float w_bce, float w_elm,
-                    const float* coord_pred, const float* coord_y, int64_t n_coord, float w_coord, void* workspace, float* expect,
-                    float* stats, float* d_expect, float* d_coord, float* bce_scale, float* total, float* bce, float* elm, float* coord,
-                    eg_stream_t stream) {
+int eg_criteria_ex_fwd(const float* logits, const float* labels, const float* valid, int batch, int64_t n_rows, const int* level_start,
+                       const int* level_side, int n_levels, const float* inv_side, float bce_ones_weight, float w_bce, float w_elm,
+                       const float* coord_pred, const float* coord_y, int64_t n_coord, float w_coord, void* workspace, float* expect,
+                       float* stats, float* d_expect, float* d_coord, float* bce_scale, float* total, float* bce, float* elm, float* coord,
+                       int bce_on_probs, int coord_l1, eg_stream_t stream) {
+    if ((bce_on_probs != 0 && bce_on_probs != 1) || (coord_l1 != 0 && coord_l1 != 1)) return set_error(EG_ERR_ARG, "bce_on_probs and coord_l1 must be 0 or 1");
     if (!logits || !labels || !valid || !inv_side || !workspace || !expect || !stats || !d_expect || !bce_scale || !total || !bce || !elm)
         return set_error(EG_ERR_ARG, "NULL argument");
     if ((coord_pred != nullptr) != (coord_y != nullptr) || (coord_pred && (!d_coord || !coord || n_coord < 1 || n_coord >= (1 << 30))))
@@ -737,19 +802,28 @@ int eg_criteria_fwd(const float* logits, const float* labels, const float* valid
     float* gt = (float*)(bce_part + criteria_bce_slots(batch, L.total_chunks) * 2);
     float* vmean = gt + (size_t)batch * n_levels * 8;
     if (tiled) {
-        hipLaunchKernelGGL(k_hm_partial<true>, dim3((unsigned)(batch * L.total_chunks)), dim3(HM_THREADS), 0, s, logits, labels, valid, hm_part, L,
-                           bce_ones_weight, bce_part);
+        if (bce_on_probs)
+            hipLaunchKernelGGL(k_hm_partial<BCE_PROBS>, dim3((unsigned)(batch * L.total_chunks)), dim3(HM_THREADS), 0, s, logits, labels, valid,
+                               hm_part, L, bce_ones_weight, bce_part);
+        else
+            hipLaunchKernelGGL(k_hm_partial<BCE_LOGITS>, dim3((unsigned)(batch * L.total_chunks)), dim3(HM_THREADS), 0, s, logits, labels, valid,
+                               hm_part, L, bce_ones_weight, bce_part);
     } else {
         blocks = ((n >> 2) + 2 * HM_THREADS - 1) / (2 * HM_THREADS);
         if (blocks < 1) blocks = 1;
         if (blocks > BCE_BLOCKS) blocks = BCE_BLOCKS;
-        hipLaunchKernelGGL(k_bce_partial, dim3((unsigned)blocks), dim3(HM_THREADS), 0, s, logits, labels, valid, n, bce_ones_weight, bce_part);
-        hipLaunchKernelGGL(k_hm_partial<false>, dim3((unsigned)(batch * L.total_chunks)), dim3(HM_THREADS), 0, s, logits, labels, valid, hm_part, L,
+        if (bce_on_probs)
+            hipLaunchKernelGGL(k_bce_partial<BCE_PROBS>, dim3((unsigned)blocks), dim3(HM_THREADS), 0, s, logits, labels, valid, n, bce_ones_weight,
+                               bce_part);
+        else
+            hipLaunchKernelGGL(k_bce_partial<BCE_LOGITS>, dim3((unsigned)blocks), dim3(HM_THREADS), 0, s, logits, labels, valid, n, bce_ones_weight,
+                               bce_part);
+        hipLaunchKernelGGL(k_hm_partial<BCE_NONE>, dim3((unsigned)(batch * L.total_chunks)), dim3(HM_THREADS), 0, s, logits, labels, valid, hm_part, L,
                            0.f, (double*)nullptr);
     }
     const int n_out = batch * n_levels * 4;
     CriteriaFinal a{expect, gt, vmean, inv_side, batch, n_levels, w_elm, d_expect, bce_part, (int)blocks, w_bce, coord_pred, coord_y,
-                    (int)n_coord, w_coord, d_coord, total, bce, elm, coord, bce_scale};
+                    (int)n_coord, w_coord, d_coord, total, bce, elm, coord, bce_scale, coord_l1};
     const unsigned n_wg = (unsigned)((n_out + 3) / 4);
     if (n_wg <= 16) {
         // a handful of workgroups (batch 1 - 2): the last one out runs the criteria's final step -- one launch (a device-scope release per
@@ -765,11 +839,24 @@ int eg_criteria_fwd(const float* logits, const float* labels, const float* valid
     return EG_OK;
 }
 
-int eg_criteria_bwd(const float* logits, const float* labels, const float* valid, int batch, int64_t n_rows, const int* level_start,
-                    const int* level_side, int n_levels, float bce_ones_weight, const float* expect, const float* stats,
-                    const float* d_expect, const float* bce_scale, const float* d_coord, int64_t n_coord, const float* g_total,
-                    const float* g_bce, const float* g_elm, const float* g_coord, float* d_logits, float* d_coord_out,
+int eg_criteria_fwd(const float* logits, const float* labels, const float* valid, int batch, int64_t n_rows, const int* level_start,
+                    const int* level_side, int n_levels, const float* inv_side, float bce_ones_weight, float w_bce, float w_elm,
+                    const float* coord_pred, const float* coord_y, int64_t n_coord, float w_coord, void* workspace, float* expect,
+                    float* stats, float* d_expect, float* d_coord, float* bce_scale, float* total, float* bce, float* elm, float* coord,
                     eg_stream_t stream) {
+    return eg_criteria_ex_fwd(logits, labels, valid, batch, n_rows, level_start, level_side, n_levels, inv_side, bce_ones_weight, w_bce,
+                              w_elm, coord_pred, coord_y, n_coord, w_coord, workspace, expect, stats, d_expect, d_coord, bce_scale, total,
+                              bce, elm, coord, 0, 0, stream);
+}
+
+// (coord_l1 is not needed here -- d_coord, the coordinate term's gradient, came out of the forward -- and is taken for the symmetry of
+//  the pair; it is checked all the same)
+int eg_criteria_ex_bwd(const float* logits, const float* labels, const float* valid, int batch, int64_t n_rows, const int* level_start,
+                       const int* level_side, int n_levels, float bce_ones_weight, const float* expect, const float* stats,
+                       const float* d_expect, const float* bce_scale, const float* d_coord, int64_t n_coord, const float* g_total,
+                       const float* g_bce, const float* g_elm, const float* g_coord, float* d_logits, float* d_coord_out,
+                       int bce_on_probs, int coord_l1, eg_stream_t stream) {
+    if ((bce_on_probs != 0 && bce_on_probs != 1) || (coord_l1 != 0 && coord_l1 != 1)) return set_error(EG_ERR_ARG, "bce_on_probs and coord_l1 must be 0 or 1");
     if (!logits || !labels || !expect || !stats || !d_expect || !bce_scale || !d_logits) return set_error(EG_ERR_ARG, "NULL argument");
     if (d_coord_out && (!d_coord || n_coord < 1)) return set_error(EG_ERR_ARG, "d_coord_out needs d_coord");
     HmLevels L{};
@@ -779,9 +866,22 @@ int eg_criteria_bwd(const float* logits, const float* labels, const float* valid
     if (d_coord_out && n_coord > n) return set_error(EG_ERR_ARG, "more coordinate elements than logit rows");
     const CriteriaBwd a{logits, labels, valid, expect, stats, d_expect, bce_scale, bce_ones_weight, g_total, g_bce, g_elm, g_coord,
                         d_coord, (int)n_coord, d_logits, d_coord_out};
-    hipLaunchKernelGGL(k_criteria_bwd, dim3((unsigned)((n + HM_THREADS - 1) / HM_THREADS)), dim3(HM_THREADS), 0, (hipStream_t)stream, a, L);
+    const dim3 grid((unsigned)((n + HM_THREADS - 1) / HM_THREADS));
+    if (bce_on_probs)
+        hipLaunchKernelGGL(k_criteria_bwd<BCE_PROBS>, grid, dim3(HM_THREADS), 0, (hipStream_t)stream, a, L);
+    else
+        hipLaunchKernelGGL(k_criteria_bwd<BCE_LOGITS>, grid, dim3(HM_THREADS), 0, (hipStream_t)stream, a, L);
     EG_HIP_TRY(hipGetLastError());
     return EG_OK;
+}
+
+int eg_criteria_bwd(const float* logits, const float* labels, const float* valid, int batch, int64_t n_rows, const int* level_start,
+                    const int* level_side, int n_levels, float bce_ones_weight, const float* expect, const float* stats,
+                    const float* d_expect, const float* bce_scale, const float* d_coord, int64_t n_coord, const float* g_total,
+                    const float* g_bce, const float* g_elm, const float* g_coord, float* d_logits, float* d_coord_out,
+                    eg_stream_t stream) {
+    return eg_criteria_ex_bwd(logits, labels, valid, batch, n_rows, level_start, level_side, n_levels, bce_ones_weight, expect, stats,
+                              d_expect, bce_scale, d_coord, n_coord, g_total, g_bce, g_elm, g_coord, d_logits, d_coord_out, 0, 0, stream);
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-"""Losses on the logits — host-side mirror of the reference's criterion classes over the HIP kernels in
+"""Losses on the model's output — host-side mirror of the reference's criterion classes over the HIP kernels in
 csrc/heatmap.hip.  Same class names, constructor arguments and ``compute`` signatures as
 ``src/core/criterion.py`` so that a criterion builder can swap them in; everything stays on the device (the
 reference's WeightedBCE round-trips the labels through numpy to build its weight tensor, criterion.py:18-21).
@@ -26,15 +26,26 @@ def _rows4(t: torch.Tensor) -> torch.Tensor:
     return t.reshape(-1, t.shape[-1]).to(torch.float32).contiguous()
 
 
-class WeightedBCEWithLogitsLoss:
-    """criterion.py:29-33 on top of WeightedBCE (:7-27): elementwise BCE-with-logits, ``ones_weight`` on the
-    positive labels, ``sum(loss * valid) / sum(valid)`` times ``loss_weight``."""
+class WeightedBCE:
+    """criterion.py:6-27: elementwise ``nn.BCELoss`` on probabilities (the loss of models built with
+    ``output_activation='sigmoid'``), ``ones_weight`` on the positive labels, ``sum(loss * valid) / sum(valid)`` times
+    ``loss_weight`` (``valid`` None: the mean).  torch raises for a probability outside [0, 1]; the kernel (eg_bce_probs_fwd) cannot,
+    so such an element makes the loss NaN."""
 
     def __init__(self, reduction, ones_weight, loss_weight):
         if reduction != "none":
             raise NotImplementedError("the reference builds this loss with reduction='none' (configs/default.yml)")
         self.ones_weight = ones_weight
         self.loss_weight = loss_weight
+
+    def compute(self, pred_y, y, valid=None):
+        x = _rows4(pred_y)
+        return self.loss_weight * ops.bce_probs(x, _rows4(y), None if valid is None else _rows4(valid), self.ones_weight)
+
+
+class WeightedBCEWithLogitsLoss(WeightedBCE):
+    """criterion.py:29-33 on top of WeightedBCE (:7-27): elementwise BCE-with-logits, ``ones_weight`` on the
+    positive labels, ``sum(loss * valid) / sum(valid)`` times ``loss_weight``."""
 
     def compute(self, pred_y, y, valid=None):
         x = _rows4(pred_y)
@@ -96,19 +107,21 @@ class LossDict(dict):
 
 
 def fused_criteria(criterion: dict, preds, y, valid, coord_preds, coord_y, batch_size: int):
-    """The criteria of engine.py:582-600 as ONE autograd node (ops.landmark_criteria) when they are exactly the configured set --
-    a WeightedBCEWithLogitsLoss and an ExpectedLandmarkMSE on the logits and optionally ``engine.MSE`` under the name
-    'coordinate' -- else None (the caller computes them one by one).  EG_FUSED_CRITERIA=0: always one by one."""
+    """The criteria of engine.py:582-600 as ONE autograd node (ops.landmark_criteria) when they are exactly a configured set --
+    one WeightedBCEWithLogitsLoss or WeightedBCE and one ExpectedLandmarkMSE on the model's output, and optionally ``engine.MSE`` or
+    ``engine.MAE`` under the name 'coordinate' (what ``build`` gives) -- else None (the caller computes them one by one).
+    EG_FUSED_CRITERIA=0: always one by one."""
     import os
+    from .engine import MAE, MSE
     if os.environ.get("EG_FUSED_CRITERIA", "1") == "0":
         return None
-    bce = [(k, c) for k, c in criterion.items() if isinstance(c, WeightedBCEWithLogitsLoss)]
+    bce = [(k, c) for k, c in criterion.items() if isinstance(c, WeightedBCE)]         # (WeightedBCEWithLogitsLoss is one)
     elm = [(k, c) for k, c in criterion.items() if isinstance(c, ExpectedLandmarkMSE)]
-    rest = [k for k, c in criterion.items() if not isinstance(c, (WeightedBCEWithLogitsLoss, ExpectedLandmarkMSE))]
+    rest = [k for k, c in criterion.items() if not isinstance(c, (WeightedBCE, ExpectedLandmarkMSE))]
     if len(bce) != 1 or len(elm) != 1 or any(k != "coordinate" for k in rest):
         return None
     coord = criterion.get("coordinate")
-    if coord is not None and (type(coord).__name__ != "MSE" or coord_preds is None or coord_y is None):
+    if coord is not None and (not isinstance(coord, (MSE, MAE)) or coord_preds is None or coord_y is None):
         return None
     if valid is None or not preds.is_cuda or elm[0][1].batch_size != batch_size:
         return None
@@ -119,9 +132,52 @@ def fused_criteria(criterion: dict, preds, y, valid, coord_preds, coord_y, batch
         inv_side = ce._side[x.device] = (1.0 / torch.tensor(ce.grid_sizes, dtype=torch.float32, device=x.device)).contiguous()
     total, vb, ve, vc = ops.landmark_criteria(x, yy, vv, batch_size, ce.levels, inv_side, cb.ones_weight, cb.loss_weight, ce.loss_weight,
                                               coord_preds if coord is not None else None, coord_y if coord is not None else None,
-                                              coord.loss_weight if coord is not None else 1.0)
+                                              coord.loss_weight if coord is not None else 1.0,
+                                              bce_on_probs=not isinstance(cb, WeightedBCEWithLogitsLoss),
+                                              coord_l1=isinstance(coord, MAE))
     out = LossDict()
     for k in criterion:                      # the caller's order
         out[k] = vb if k == kb else (ve if k == ke else vc)
     out.total = total
     return out
+
+
+# src/builders/criterion_builder.py's names
+CRITERIA = {"bce": WeightedBCE, "WeightedBceWithLogits": WeightedBCEWithLogitsLoss, "ExpectedLandmarkMse": ExpectedLandmarkMSE}
+# the reference's other names: criteria with a two-argument compute(pred_y, y) -- see build()
+_UNREACHABLE = ("mse", "mae", "HeatmapMse")
+
+
+def build(criterion_config, logger=None) -> dict:
+    """src/builders/criterion_builder.py: {name: criterion} in the order of ``criterion_config``, plus ``'coordinate': engine.MAE()``
+    when ``use_coordinate_graph`` is set.  The keys ``batch_size``, ``frame_size``, ``num_aux_graphs``, ``use_main_graph_only``,
+    ``use_coordinate_graph`` and ``num_output_channels`` (what the reference's engine adds, engine.py:123-131) configure
+    ExpectedLandmarkMse and the coordinate criterion; every other key names a criterion and maps to its constructor arguments.
+    The dictionary goes to ``engine.compute_loss``, which runs the set as one node (``fused_criteria``)."""
+    from .engine import MAE
+    config = dict(criterion_config)
+    batch_size = config.pop("batch_size")
+    frame_size = config.pop("frame_size")
+    num_aux_graphs = config.pop("num_aux_graphs")
+    use_main_graph_only = config.pop("use_main_graph_only")
+    use_coordinate_graph = config.pop("use_coordinate_graph")
+    num_output_channels = config.pop("num_output_channels")
+    criteria = {}
+    for name, kwargs in config.items():
+        if name == "ExpectedLandmarkMse":
+            criteria[name] = ExpectedLandmarkMSE(batch_size=batch_size, frame_size=frame_size, num_aux_graphs=num_aux_graphs,
+                                                 use_main_graph_only=use_main_graph_only, num_output_channels=num_output_channels,
+                                                 **kwargs)
+        elif name in CRITERIA:
+            criteria[name] = CRITERIA[name](**kwargs)
+        elif name in _UNREACHABLE:
+            raise NotImplementedError(f"criterion {name!r} is not implemented: its compute(pred_y, y) takes two arguments and the "
+                                      "reference's engine calls every criterion but 'coordinate' with three (src/engine.py:592-598), "
+                                      "so the reference cannot run it either")
+        else:
+            raise KeyError(f"unknown criterion {name!r}")
+        if logger is not None and hasattr(logger, "infov"):
+            logger.infov("{} criterion is built.".format(name.upper()))
+    if use_coordinate_graph:
+        criteria["coordinate"] = MAE()
+    return criteria

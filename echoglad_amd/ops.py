@@ -989,7 +989,17 @@ def elm_reduce(expect, gt, vmean, inv_side, weight: float):
 
 def bce_logits_fwd(logits, labels, valid, ones_weight: float) -> torch.Tensor:
     """[sum(w * bce * valid), sum(valid), ratio] as a float32 device tensor (no host sync)."""
-    for name, t in (("logits", logits), ("labels", labels)):
+    return _bce_fwd(logits, labels, valid, ones_weight, False)
+
+
+def bce_probs_fwd(probs, labels, valid, ones_weight: float) -> torch.Tensor:
+    """bce_logits_fwd for probabilities (nn.BCELoss's element formula; an element outside [0, 1] makes the loss NaN)."""
+    return _bce_fwd(probs, labels, valid, ones_weight, True)
+
+
+def _bce_fwd(logits, labels, valid, ones_weight: float, probs: bool) -> torch.Tensor:
+    what = "eg_bce_probs_fwd" if probs else "eg_bce_logits_fwd"
+    for name, t in (("probs" if probs else "logits", logits), ("labels", labels)):
         if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
             raise RuntimeError(f"{name} must be a contiguous CUDA float32 tensor")
     if labels.numel() != logits.numel() or (valid is not None and valid.numel() != logits.numel()):
@@ -1000,17 +1010,17 @@ def bce_logits_fwd(logits, labels, valid, ones_weight: float) -> torch.Tensor:
     one = (ct.c_int * 1)(1)
     ws = _hm_workspace(logits.device, int(lib.eg_heatmap_workspace_bytes(1, one, 1)))
     out = torch.empty(3, dtype=torch.float32, device=logits.device)
-    _lib.check(lib.eg_bce_logits_fwd(_ptr(logits), _ptr(labels), _ptr(valid), logits.numel(), ct.c_float(ones_weight),
-                                     _ptr(ws), _ptr(out), _stream()), "eg_bce_logits_fwd")
+    _lib.check(getattr(lib, what)(_ptr(logits), _ptr(labels), _ptr(valid), logits.numel(), ct.c_float(ones_weight),
+                                  _ptr(ws), _ptr(out), _stream()), what)
     return out
 
 
 class _BCELogitsFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, labels, valid, ones_weight):
-        out = bce_logits_fwd(logits, labels, valid, ones_weight)
+    def forward(ctx, logits, labels, valid, ones_weight, probs=False):
+        out = _bce_fwd(logits, labels, valid, ones_weight, probs)
         ctx.save_for_backward(logits, labels, valid if valid is not None else logits.new_zeros(0), out)
-        ctx.ones_weight, ctx.has_valid = ones_weight, valid is not None
+        ctx.ones_weight, ctx.has_valid, ctx.probs = ones_weight, valid is not None, probs
         return out[2]
 
     @staticmethod
@@ -1018,15 +1028,22 @@ class _BCELogitsFn(torch.autograd.Function):
         logits, labels, valid, out = ctx.saved_tensors
         scale = (g / out[1]).reshape(1).to(torch.float32).contiguous()
         dx = torch.empty_like(logits)
-        _lib.check(_lib.load().eg_bce_logits_bwd(_ptr(logits), _ptr(labels), _ptr(valid) if ctx.has_valid else None,
-                                                 logits.numel(), ct.c_float(ctx.ones_weight), _ptr(scale), _ptr(dx), _stream()),
-                   "eg_bce_logits_bwd")
-        return dx, None, None, None
+        what = "eg_bce_probs_bwd" if ctx.probs else "eg_bce_logits_bwd"
+        _lib.check(getattr(_lib.load(), what)(_ptr(logits), _ptr(labels), _ptr(valid) if ctx.has_valid else None,
+                                              logits.numel(), ct.c_float(ctx.ones_weight), _ptr(scale), _ptr(dx), _stream()), what)
+        return dx, None, None, None, None
 
 
 def bce_logits(logits, labels, valid=None, ones_weight: float = 1.0) -> torch.Tensor:
     """sum(w * bce_with_logits(x, y) * valid) / sum(valid), w = ones_weight where y == 1 (autograd wrt logits)."""
     return _BCELogitsFn.apply(logits, labels, valid, float(ones_weight))
+
+
+def bce_probs(probs, labels, valid=None, ones_weight: float = 1.0) -> torch.Tensor:
+    """sum(w * bce(p, y) * valid) / sum(valid) on probabilities (nn.BCELoss's element formula: log clamped at -100, gradient
+    (p - y) / max((1 - p) p, 1e-12)), w = ones_weight where y == 1 (autograd wrt probs).  torch raises for p outside [0, 1]; the
+    kernel cannot (it may be captured into a graph): such an element makes the result NaN, whatever its valid."""
+    return _BCELogitsFn.apply(probs, labels, valid, float(ones_weight), True)
 
 
 CONFUSION_MAX_CHANNELS = 8
@@ -1065,12 +1082,13 @@ def confusion_counts(pred: torch.Tensor, y: torch.Tensor, valid: torch.Tensor, h
 
 
 class _CriteriaFn(torch.autograd.Function):
-    """WeightedBCEWithLogitsLoss + ExpectedLandmarkMSE (+ MSE on the landmark coordinates) of one training step as ONE autograd
-    node over eg_criteria_fwd / eg_criteria_bwd: (logits [B*n,4], coord_pred [R,2] | None) -> (total, bce, elm, coord | None),
-    every output a 0-d tensor that can be backpropagated on its own or summed (engine.py:582-600, :271)."""
+    """WeightedBCEWithLogitsLoss or WeightedBCE + ExpectedLandmarkMSE (+ MSE or MAE on the landmark coordinates) of one training step
+    as ONE autograd node over eg_criteria_ex_fwd / eg_criteria_ex_bwd: (logits [B*n,4], coord_pred [R,2] | None) -> (total, bce, elm,
+    coord | None), every output a 0-d tensor that can be backpropagated on its own or summed (engine.py:582-600, :271)."""
 
     @staticmethod
-    def forward(ctx, logits, coord_pred, labels, valid, coord_y, batch, levels, inv_side, ones_weight, w_bce, w_elm, w_coord):
+    def forward(ctx, logits, coord_pred, labels, valid, coord_y, batch, levels, inv_side, ones_weight, w_bce, w_elm, w_coord, bce_on_probs,
+                coord_l1):
         dev = logits.device
         n_rows = logits.shape[0] // batch
         start, side, n = _level_arrays(levels)
@@ -1086,12 +1104,12 @@ class _CriteriaFn(torch.autograd.Function):
         bce_scale = torch.empty(1, dtype=torch.float32, device=dev)
         total, vb, ve = (torch.empty((), dtype=torch.float32, device=dev) for _ in range(3))
         vc = torch.empty((), dtype=torch.float32, device=dev) if has_coord else None
-        _lib.check(lib.eg_criteria_fwd(_ptr(logits), _ptr(labels), _ptr(valid), batch, n_rows, start, side, n, _ptr(inv_side),
-                                       ct.c_float(ones_weight), ct.c_float(w_bce), ct.c_float(w_elm), _ptr(cp), _ptr(cy),
-                                       cp.numel() if has_coord else 0, ct.c_float(w_coord), _ptr(ws), _ptr(expect), _ptr(stats),
-                                       _ptr(d_expect), _ptr(d_coord), _ptr(bce_scale), _ptr(total), _ptr(vb), _ptr(ve), _ptr(vc),
-                                       _stream()), "eg_criteria_fwd")
-        ctx.meta = (batch, levels, ones_weight, has_coord)
+        _lib.check(lib.eg_criteria_ex_fwd(_ptr(logits), _ptr(labels), _ptr(valid), batch, n_rows, start, side, n, _ptr(inv_side),
+                                          ct.c_float(ones_weight), ct.c_float(w_bce), ct.c_float(w_elm), _ptr(cp), _ptr(cy),
+                                          cp.numel() if has_coord else 0, ct.c_float(w_coord), _ptr(ws), _ptr(expect), _ptr(stats),
+                                          _ptr(d_expect), _ptr(d_coord), _ptr(bce_scale), _ptr(total), _ptr(vb), _ptr(ve), _ptr(vc),
+                                          int(bce_on_probs), int(coord_l1), _stream()), "eg_criteria_ex_fwd")
+        ctx.meta = (batch, levels, ones_weight, has_coord, int(bce_on_probs), int(coord_l1))
         ctx.save_for_backward(logits, labels, valid, expect, stats, d_expect, bce_scale, d_coord if has_coord else logits.new_zeros(0))
         ctx.set_materialize_grads(False)
         return total, vb, ve, vc
@@ -1099,29 +1117,31 @@ class _CriteriaFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_total, g_bce, g_elm, g_coord):
         logits, labels, valid, expect, stats, d_expect, bce_scale, d_coord = ctx.saved_tensors
-        batch, levels, ones_weight, has_coord = ctx.meta
+        batch, levels, ones_weight, has_coord, bce_on_probs, coord_l1 = ctx.meta
         start, side, n = _level_arrays(levels)
         gs = [None if g is None else g.to(torch.float32).reshape(1).contiguous() for g in (g_total, g_bce, g_elm, g_coord)]
         d_logits = torch.empty_like(logits)
         want_coord = has_coord and ctx.needs_input_grad[1]
         d_coord_out = torch.empty_like(d_coord) if want_coord else None
-        _lib.check(_lib.load().eg_criteria_bwd(_ptr(logits), _ptr(labels), _ptr(valid), batch, logits.shape[0] // batch, start, side, n,
-                                               ct.c_float(ones_weight), _ptr(expect), _ptr(stats), _ptr(d_expect), _ptr(bce_scale),
-                                               _ptr(d_coord) if want_coord else None, d_coord.numel() if want_coord else 0,
-                                               _ptr(gs[0]), _ptr(gs[1]), _ptr(gs[2]), _ptr(gs[3]), _ptr(d_logits), _ptr(d_coord_out),
-                                               _stream()), "eg_criteria_bwd")
-        return (d_logits, d_coord_out) + (None,) * 10
+        _lib.check(_lib.load().eg_criteria_ex_bwd(_ptr(logits), _ptr(labels), _ptr(valid), batch, logits.shape[0] // batch, start, side,
+                                                  n, ct.c_float(ones_weight), _ptr(expect), _ptr(stats), _ptr(d_expect), _ptr(bce_scale),
+                                                  _ptr(d_coord) if want_coord else None, d_coord.numel() if want_coord else 0,
+                                                  _ptr(gs[0]), _ptr(gs[1]), _ptr(gs[2]), _ptr(gs[3]), _ptr(d_logits), _ptr(d_coord_out),
+                                                  bce_on_probs, coord_l1, _stream()), "eg_criteria_ex_bwd")
+        return (d_logits, d_coord_out) + (None,) * 12
 
 
 def landmark_criteria(logits, labels, valid, batch: int, levels, inv_side, ones_weight: float, w_bce: float, w_elm: float,
-                      coord_pred=None, coord_y=None, w_coord: float = 1.0):
-    """-> (total, bce, elm, coord | None): the step's criteria as one autograd node (5 launches forward + backward)."""
+                      coord_pred=None, coord_y=None, w_coord: float = 1.0, bce_on_probs: bool = False, coord_l1: bool = False):
+    """-> (total, bce, elm, coord | None): the step's criteria as one autograd node (5 launches forward + backward).
+    bce_on_probs: the BCE term is WeightedBCE's on probabilities (bce_probs) instead of WeightedBCEWithLogitsLoss's; coord_l1: the
+    coordinate term is MAE (w_coord * mean|coord_pred - coord_y|) instead of MSE."""
     for name, t in (("logits", logits), ("labels", labels), ("valid", valid)):
         _check_logits(t, name, logits.shape[0])
     if any(t.data_ptr() % 16 for t in (logits, labels, valid)):
         logits, labels, valid = (t if t.data_ptr() % 16 == 0 else t.clone() for t in (logits, labels, valid))
     return _CriteriaFn.apply(logits, coord_pred, labels, valid, coord_y, int(batch), levels, inv_side, float(ones_weight), float(w_bce),
-                             float(w_elm), float(w_coord))
+                             float(w_elm), float(w_coord), bool(bce_on_probs), bool(coord_l1))
 
 
 # ---------------------------------------------------------------------------

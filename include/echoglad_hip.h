@@ -85,8 +85,8 @@ extern "C" {
  * 134: eg_dropout_epoch_add / _set, eg_debug_dropout_epoch (round 5: a whole train step as one HIP graph).
  * 135: eg_gcn_layer_bwd_lower, eg_bilinear4_bwd_rows_sums, eg_avg_pool_pyramid_fwd / _bwd, eg_criteria_* (round 6).
  * 136: eg_classifier_train_fwd_act(h_sparse), eg_classifier_bwd_sums(layer_residual, recompute_h).  137, 138: eg_coord_update_fwd / _bwd.  139, 140: eg_adam_step.
- * 141: eg_confusion_counts. */
-#define EG_ABI_VERSION 141
+ * 141: eg_confusion_counts.  142: eg_bce_probs_fwd / _bwd, eg_criteria_ex_fwd / _bwd. */
+#define EG_ABI_VERSION 142
 
 #define EG_CHANNELS 128 /* node_embedding_dim == node_hidden_dim (configs/default.yml:13-14) */
 
@@ -536,7 +536,12 @@ int eg_adam_step(const eg_adam_tensor* tensors, int count, float* steps, float l
  * eg_heatmap_expect_bwd: d_logits[r,c] = p[r,c] * ((h - E_h) dE_h + (w - E_w) dE_w), rows outside every level 0.
  * eg_bce_logits_fwd: out3 = { sum(w * bce(x, y) * valid), sum(valid), their ratio }, w = ones_weight where
  *   y == 1 (when ones_weight > 1) else 1; valid may be NULL (= 1).  fp64 sums in a fixed order.
- * eg_bce_logits_bwd: d_logits = (sigmoid(x) - y) * w * valid * scale_dev[0]. */
+ * eg_bce_logits_bwd: d_logits = (sigmoid(x) - y) * w * valid * scale_dev[0].
+ * eg_bce_probs_fwd / _bwd: the same on probabilities p (nn.BCELoss, the reference's WeightedBCE, criterion.py:6-27) with torch's
+ *   element formula bce(p, y) = (y - 1) max(log1p(-p), -100) - y max(log p, -100) and gradient
+ *   d_probs = (p - y) / max((1 - p) p, 1e-12) * w * valid * scale_dev[0].  torch raises for p outside [0, 1]; these cannot (they may
+ *   be captured into a graph), so an element outside [0, 1] or NaN makes the loss (out3[0], out3[2]) NaN -- whatever its valid --
+ *   and its own gradient NaN. */
 size_t eg_heatmap_workspace_bytes(int batch, const int* level_side, int n_levels);
 int eg_heatmap_expect_fwd(const float* logits, const float* labels, const float* valid, int batch, int64_t n_rows,
                           const int* level_start, const int* level_side, int n_levels, void* workspace, float* expect,
@@ -553,6 +558,10 @@ int eg_bce_logits_fwd(const float* logits, const float* labels, const float* val
                       void* workspace, float* out3, eg_stream_t stream);
 int eg_bce_logits_bwd(const float* logits, const float* labels, const float* valid, int64_t n, float ones_weight,
                       const float* scale_dev, float* d_logits, eg_stream_t stream);
+int eg_bce_probs_fwd(const float* probs, const float* labels, const float* valid, int64_t n, float ones_weight,
+                     void* workspace, float* out3, eg_stream_t stream);
+int eg_bce_probs_bwd(const float* probs, const float* labels, const float* valid, int64_t n, float ones_weight,
+                     const float* scale_dev, float* d_probs, eg_stream_t stream);
 
 /* ---- the criteria of a training step as ONE node (src/engine.py:582-600: the sum of WeightedBCEWithLogitsLoss, ExpectedLandmarkMSE
  * and, with the coordinate graph, MSE on the landmark coordinates -- criterion.py:13-27, :36-48, :93-151).
@@ -561,7 +570,14 @@ int eg_bce_logits_bwd(const float* logits, const float* labels, const float* val
  *   *total = their sum.  Kept for the backward: expect, stats [batch,n_levels,4,2], d_expect (= d elm / d expect), d_coord [n_coord]
  *   (= d coord / d coord_pred), bce_scale [1].  inv_side: DEVICE [n_levels] = 1 / level side.  workspace: eg_criteria_workspace_bytes().
  * eg_criteria_bwd (1 launch): d_logits = (g_total + g_bce) * d bce / d logits + (g_total + g_elm) * d elm / d logits,
- *   d_coord_out (nullable) = (g_total + g_coord) * d_coord;  g_*: upstream gradients as DEVICE scalars, each nullable (= 0). */
+ *   d_coord_out (nullable) = (g_total + g_coord) * d_coord;  g_*: upstream gradients as DEVICE scalars, each nullable (= 0).
+ * eg_criteria_ex_fwd / _bwd: the same with two more arguments (eg_criteria_* are their (0, 0) case, bit for bit), each 0 or 1:
+ *   bce_on_probs = 1: the BCE term is eg_bce_probs_fwd's on the `logits` array read as probabilities (WeightedBCE, criterion.py:6-27;
+ *     NaN rule as there); ExpectedLandmarkMSE still takes its softmax over the same array, as the reference's engine gives both
+ *     criteria the model's output.  _bwd must get the same value.
+ *   coord_l1 = 1: *coord = w_coord * mean|coord_pred - coord_y| (MAE, criterion.py:51-63), d_coord = w_coord sign(pred - y) / n_coord
+ *     with sign(0) = 0 (torch's l1_loss backward).  The backward does not depend on it.
+ *   Same launches as eg_criteria_*, no host synchronisation, no allocation. */
 size_t eg_criteria_workspace_bytes(int batch, const int* level_side, int n_levels);
 int eg_criteria_fwd(const float* logits, const float* labels, const float* valid, int batch, int64_t n_rows, const int* level_start,
                     const int* level_side, int n_levels, const float* inv_side, float bce_ones_weight, float w_bce, float w_elm,
@@ -573,6 +589,16 @@ int eg_criteria_bwd(const float* logits, const float* labels, const float* valid
                     const float* d_expect, const float* bce_scale, const float* d_coord, int64_t n_coord, const float* g_total,
                     const float* g_bce, const float* g_elm, const float* g_coord, float* d_logits, float* d_coord_out,
                     eg_stream_t stream);
+int eg_criteria_ex_fwd(const float* logits, const float* labels, const float* valid, int batch, int64_t n_rows, const int* level_start,
+                       const int* level_side, int n_levels, const float* inv_side, float bce_ones_weight, float w_bce, float w_elm,
+                       const float* coord_pred, const float* coord_y, int64_t n_coord, float w_coord, void* workspace, float* expect,
+                       float* stats, float* d_expect, float* d_coord, float* bce_scale, float* total, float* bce, float* elm, float* coord,
+                       int bce_on_probs, int coord_l1, eg_stream_t stream);
+int eg_criteria_ex_bwd(const float* logits, const float* labels, const float* valid, int batch, int64_t n_rows, const int* level_start,
+                       const int* level_side, int n_levels, float bce_ones_weight, const float* expect, const float* stats,
+                       const float* d_expect, const float* bce_scale, const float* d_coord, int64_t n_coord, const float* g_total,
+                       const float* g_bce, const float* g_elm, const float* g_coord, float* d_logits, float* d_coord_out,
+                       int bce_on_probs, int coord_l1, eg_stream_t stream);
 
 /* ---- confusion counts of the landmark classifier (reference: BalancedBinaryAccuracyEvaluator, src/core/evaluators.py:85-143) --
  * pred, y, valid: [rows, channels] f32 (1 <= channels <= 8, rows >= 1).  For every channel c, over the rows with valid > 0:
