@@ -15,7 +15,7 @@ LIB_PATH = Path(os.environ.get("ECHOGLAD_LIB", _PKG / "lib" / "libechoglad_hip.s
 HEADER_PATH = _PKG.parent / "include" / "echoglad_hip.h"
 
 EG_OK, EG_ERR_ARG, EG_ERR_UNSUPPORTED, EG_ERR_HIP = 0, -1, -2, -3
-ABI_VERSION = 142          # EG_ABI_VERSION of include/echoglad_hip.h that SIGNATURES below was written for
+ABI_VERSION = 143          # EG_ABI_VERSION of include/echoglad_hip.h that SIGNATURES below was written for
 
 _lib: Optional[ct.CDLL] = None
 
@@ -133,6 +133,9 @@ SIGNATURES: Dict[str, tuple] = {
     "eg_bce_probs_fwd": (_i, [_p, _p, _p, _i64, ct.c_float, _p, _p, _p]),
     "eg_bce_probs_bwd": (_i, [_p, _p, _p, _i64, ct.c_float, _p, _p, _p]),
     "eg_confusion_counts": (_i, [_p, _p, _p, _i64, _i, _p, ct.c_size_t, _p, _i64, _p, _p]),
+    "eg_landmark_record_workspace_bytes": (ct.c_size_t, [_i, _i]),
+    "eg_landmark_record_hm": (_i, [_p, _p, _p, _i, _i64, _i, _p, _p, _p, ct.c_size_t, _p, _p, _i64, _p, _p]),
+    "eg_landmark_record_coord": (_i, [_p, _p, _i, _p, _p, _p, _p, _i64, _p, _p]),
 }
 
 

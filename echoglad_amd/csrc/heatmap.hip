@@ -645,6 +645,123 @@ __global__ __launch_bounds__(HM_THREADS) void k_criteria_bwd(const CriteriaBwd a
     *reinterpret_cast<float4*>(a.d_logits + (size_t)t * 4) = float4{o[0], o[1], o[2], o[3]};
 }
 
+// ---- the landmark evaluator's record (LandmarkExpectedCoordiantesEvaluator.update, src/core/evaluators.py:291-391) -------------
+// One update appends one record to a device-side history at *counter and advances the counter: coordinate errors, valid flags,
+// width MAE / MPE, and a per-frame detail block (pred / gt (h, w) of the 4 landmarks, the 6 widths in mm).  The host class's fp32
+// arithmetic in its operation order, no contraction into FMAs (the host's torch / numpy ops do not fuse), sums over the frames
+// in ascending frame order: bit-reproducible, and the host's IEEE results where a landmark has no valid row (flag false, divisor
+// 1) or a ground-truth width is zero (MPE inf or NaN).
+constexpr int LM_REC = 16;          // floats per record: err[4], valid[4], MAE {ivs, lvid, lvpw}, MPE {ivs, lvid, lvpw}, 2 spare
+constexpr int LM_DETAIL = 24;       // floats per frame: pred[4][2], gt[4][2], pred widths {ivs, lvid, lvpw}, gt widths, 2 spare
+constexpr int LM_TERMS = 10;        // per-frame terms summed over the frames: err * vs [4], MAE * w [3], MPE * w [3]
+constexpr int LM_THREADS = 256;
+
+struct LmRecord {
+    const float *pred, *gt;         // [B,4,2] (h, w)
+    const float* vmean;             // [B,4] mean of valid per (frame, landmark); NULL: every landmark valid
+    const float *pix2mm_x, *pix2mm_y;   // [B]
+    int batch;
+    float* history;                 // [capacity][LM_REC]
+    float* detail;                  // [capacity][B][LM_DETAIL]
+    long long capacity;
+    long long* counter;
+};
+
+// evaluators.py:619-620 pixel_length: sqrt(((x0 - x1) px)^2 + ((y0 - y1) py)^2)
+__device__ inline float lm_length(float x0, float y0, float x1, float y1, float px, float py) {
+#pragma clang fp contract(off)
+    const float a = (x0 - x1) * px, b = (y0 - y1) * py;
+    return sqrtf(a * a + b * b);
+}
+
+// (every thread of a LM_THREADS workgroup comes here)
+__device__ inline void lm_record_body(const LmRecord& a) {
+#pragma clang fp contract(off)
+    __shared__ float s_nv[4];
+    __shared__ float s_terms[LM_THREADS][LM_TERMS + 1];
+    __shared__ float s_sum[LM_TERMS];
+    __shared__ long long s_rec;
+    const int t = threadIdx.x;
+    if (t == 0) s_rec = *a.counter;
+    if (t < 4) {                                     // nv = vs.sum(dim=0), frames in order
+        float nv = 0.f;
+        for (int b = 0; b < a.batch; ++b) nv += a.vmean ? a.vmean[(size_t)b * 4 + t] : 1.f;
+        s_nv[t] = nv;
+    }
+    if (t < LM_TERMS) s_sum[t] = 0.f;
+    __syncthreads();
+    const long long rec = s_rec;
+    const bool keep = rec < a.capacity;              // past capacity: nothing written, the counter still advances
+    float nv[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) nv[c] = s_nv[c] == 0.f ? 1.f : s_nv[c];
+    const float nv_lvid = nv[0] < nv[1] ? nv[0] : nv[1];     // torch.min(nv[0, 0], nv[0, 1])
+    // frames in chunks of LM_THREADS, one per thread; the chunk's terms are added to the running sums in frame order
+    for (int b0 = 0; b0 < a.batch; b0 += LM_THREADS) {
+        const int b = b0 + t;
+        if (b < a.batch) {
+            float p[8], g[8], vs[4];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { p[k] = a.pred[(size_t)b * 8 + k]; g[k] = a.gt[(size_t)b * 8 + k]; }
+#pragma unroll
+            for (int c = 0; c < 4; ++c) vs[c] = a.vmean ? a.vmean[(size_t)b * 4 + c] : 1.f;
+            const float px = a.pix2mm_x[b], py = a.pix2mm_y[b];
+            float* q = s_terms[t];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) q[c] = lm_length(g[2 * c + 1], g[2 * c], p[2 * c + 1], p[2 * c], px, py) * vs[c];
+            // calculate_widths (evaluators.py:393-407): ivs = |3 - 0|, lvid = |0 - 1|, lvpw = |1 - 2|
+            const float wp[3] = {lm_length(p[7], p[6], p[1], p[0], px, py), lm_length(p[1], p[0], p[3], p[2], px, py),
+                                 lm_length(p[3], p[2], p[5], p[4], px, py)};
+            const float wg[3] = {lm_length(g[7], g[6], g[1], g[0], px, py), lm_length(g[1], g[0], g[3], g[2], px, py),
+                                 lm_length(g[3], g[2], g[5], g[4], px, py)};
+            const float w[3] = {vs[3] / nv[3], (vs[0] * vs[1]) / nv_lvid, vs[2] / nv[2]};
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float d = fabsf(wp[k] - wg[k]);
+                q[4 + k] = d * w[k];
+                q[7 + k] = ((100.0f * d) / wg[k]) * w[k];
+            }
+            if (keep) {
+                float* o = a.detail + ((size_t)rec * a.batch + b) * LM_DETAIL;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) { o[k] = p[k]; o[8 + k] = g[k]; }
+#pragma unroll
+                for (int k = 0; k < 3; ++k) { o[16 + k] = wp[k]; o[19 + k] = wg[k]; }
+                o[22] = 0.f; o[23] = 0.f;
+            }
+        }
+        __syncthreads();
+        if (t < LM_TERMS) {
+            const int n = min(LM_THREADS, a.batch - b0);
+            float s = s_sum[t];
+            for (int k = 0; k < n; ++k) s += s_terms[k][t];
+            s_sum[t] = s;
+        }
+        __syncthreads();
+    }
+    if (keep && t < LM_REC) {
+        float v = 0.f;
+        if (t < 4) v = s_sum[t] / nv[t];
+        else if (t < 8) v = s_nv[t - 4] > 0.f ? 1.f : 0.f;
+        else if (t < 14) v = s_sum[t - 4];
+        a.history[(size_t)rec * LM_REC + t] = v;
+    }
+    if (t == 0) *a.counter = rec + 1;
+}
+
+// heat-map models: k_hm_final's decode of the main grid and, in the workgroup that finishes last, the record -- with k_hm_partial
+// in front, an update is two launches (the decode alone was two)
+__global__ __launch_bounds__(LM_THREADS) void k_hm_final_record(const double* __restrict__ part, float* __restrict__ expect,
+                                                                float* __restrict__ gt, float* __restrict__ vmean, const HmLevels L,
+                                                                const LmRecord a, unsigned* ticket) {
+    hm_final_wave(part, expect, nullptr, (int64_t*)nullptr, gt, vmean, L);
+    if (last_workgroup_out(ticket, gridDim.x)) lm_record_body(a);
+}
+
+// coordinate-graph models: the record from the predicted and labelled coordinates, every landmark valid
+__global__ __launch_bounds__(LM_THREADS) void k_lm_record(const LmRecord a) { lm_record_body(a); }
+
+
 }  // namespace eg
 
 using namespace eg;
@@ -882,6 +999,66 @@ int eg_criteria_bwd(const float* logits, const float* labels, const float* valid
                     eg_stream_t stream) {
     return eg_criteria_ex_bwd(logits, labels, valid, batch, n_rows, level_start, level_side, n_levels, bce_ones_weight, expect, stats,
                               d_expect, bce_scale, d_coord, n_coord, g_total, g_bce, g_elm, g_coord, d_logits, d_coord_out, 0, 0, stream);
+}
+
+}  // extern "C"
+
+extern "C" {
+
+size_t eg_landmark_record_workspace_bytes(int batch, int frame) {
+    if (batch < 1 || frame < 1) return 0;
+    const size_t chunks = ((size_t)frame * frame + HM_CHUNK - 1) / HM_CHUNK;
+    return (size_t)batch * chunks * 4 * HM_REC * sizeof(double) + (size_t)batch * 20 * sizeof(float);
+}
+
+static int lm_record_check(const float* pix2mm_x, const float* pix2mm_y, int batch, float* history, float* detail, int64_t capacity,
+                           int64_t* counter) {
+    if (!pix2mm_x || !pix2mm_y || !history || !detail || !counter) return set_error(EG_ERR_ARG, "NULL argument");
+    if (batch < 1) return set_error(EG_ERR_ARG, "batch must be >= 1");
+    if (capacity < 1) return set_error(EG_ERR_ARG, "capacity must be >= 1");
+    if ((uintptr_t)counter % 8) return set_error(EG_ERR_ARG, "misaligned counter");
+    return EG_OK;
+}
+
+int eg_landmark_record_hm(const float* logits, const float* labels, const float* valid, int batch, int64_t n_rows, int frame,
+                          const float* pix2mm_x, const float* pix2mm_y, void* workspace, size_t workspace_bytes, float* history,
+                          float* detail, int64_t capacity, int64_t* counter, eg_stream_t stream) {
+    if (!logits || !labels || !valid || !workspace) return set_error(EG_ERR_ARG, "NULL argument");
+    int rc = lm_record_check(pix2mm_x, pix2mm_y, batch, history, detail, capacity, counter);
+    if (rc != EG_OK) return rc;
+    if ((uintptr_t)workspace % 8) return set_error(EG_ERR_ARG, "misaligned workspace");
+    if (((uintptr_t)logits | (uintptr_t)labels | (uintptr_t)valid) & 15) return set_error(EG_ERR_ARG, "logits / labels / valid must be 16-byte aligned");
+    if (frame < 1 || (int64_t)frame * frame > n_rows) return set_error(EG_ERR_ARG, "the main grid does not fit in the frame's rows");
+    if (workspace_bytes < eg_landmark_record_workspace_bytes(batch, frame)) return set_error(EG_ERR_ARG, "workspace too small");
+    const int start = (int)(n_rows - (int64_t)frame * frame), side = frame;
+    HmLevels L{};
+    rc = fill_levels(batch, n_rows, &start, &side, 1, L);
+    if (rc != EG_OK) return rc;
+    unsigned* ticket = eg_ticket_ptr((void*)stream, 4);
+    if (!ticket) return set_error(EG_ERR_HIP, "no device memory for a ticket word");
+    double* part = (double*)workspace;
+    float* expect = (float*)(part + (size_t)batch * L.total_chunks * 4 * HM_REC);
+    float* gt = expect + (size_t)batch * 8;
+    float* vmean = gt + (size_t)batch * 8;
+    const LmRecord a{expect, gt, vmean, pix2mm_x, pix2mm_y, batch, history, detail, (long long)capacity, (long long*)counter};
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_hm_partial<BCE_NONE>, dim3((unsigned)(batch * L.total_chunks)), dim3(HM_THREADS), 0, s, logits, labels, valid,
+                       part, L, 0.f, (double*)nullptr);
+    hipLaunchKernelGGL(k_hm_final_record, dim3((unsigned)batch), dim3(LM_THREADS), 0, s, (const double*)part, expect, gt, vmean, L, a,
+                       ticket);
+    EG_HIP_TRY(hipGetLastError());
+    return EG_OK;
+}
+
+int eg_landmark_record_coord(const float* coord_pred, const float* coord_y, int batch, const float* pix2mm_x, const float* pix2mm_y,
+                             float* history, float* detail, int64_t capacity, int64_t* counter, eg_stream_t stream) {
+    if (!coord_pred || !coord_y) return set_error(EG_ERR_ARG, "NULL argument");
+    const int rc = lm_record_check(pix2mm_x, pix2mm_y, batch, history, detail, capacity, counter);
+    if (rc != EG_OK) return rc;
+    const LmRecord a{coord_pred, coord_y, nullptr, pix2mm_x, pix2mm_y, batch, history, detail, (long long)capacity, (long long*)counter};
+    hipLaunchKernelGGL(k_lm_record, dim3(1), dim3(LM_THREADS), 0, (hipStream_t)stream, a);
+    EG_HIP_TRY(hipGetLastError());
+    return EG_OK;
 }
 
 }  // extern "C"

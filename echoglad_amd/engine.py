@@ -5,6 +5,7 @@ evaluators.  Logging, checkpointing and wandb of the reference are out of scope 
 """
 from __future__ import annotations
 
+import copy
 from typing import Dict, Optional
 
 import torch
@@ -171,6 +172,148 @@ class GraphedTrainStep:
             torch.autograd.graph.increment_version(self._written)
         self.replays += 1
         return self.outputs
+
+
+def _state_key(module: torch.nn.Module) -> tuple:
+    """What a captured graph over ``module`` depends on: every parameter's and buffer's in-place version and address."""
+    return tuple((t._version, t.data_ptr()) for t in list(module.parameters()) + list(module.buffers()))
+
+
+def _record_counter(ev):
+    """The device record counter of a capturable evaluator (None before its history exists)."""
+    st = ev._state
+    return None if st is None else st[3]
+
+
+class GraphedEvalStep:
+    """One WHOLE evaluation step -- embedder, landmark model, criteria, every evaluator's update and the epoch's loss meter
+    (engine.py:340-460 of the reference for one batch) -- captured once into a HIP graph and replayed.  The evaluation counterpart
+    of ``GraphedTrainStep``; it covers coordinate-graph models, which the model-level ``enable_hip_graph`` replay does not.
+
+    ``static_batch``: a collated batch on the device (``data.to_device``); write every new batch INTO it (``data.copy_batch_``) before
+    calling the step.  ``pix2mm_x / pix2mm_y`` must be device tensors.  The graph reads ``static_batch.node_coords`` into a private
+    buffer first: the caller's tensor is never written.  ``step()`` -> (preds, coord_preds, losses), the graph's static outputs, valid
+    until the next call.  ``loss_avg()`` is the reference's ``loss_meter.avg`` (meters.AverageEpochMeter: an fp64 sum of
+    ``total_loss * batch_size`` over an fp64 count, kept on the device and read back only there); ``reset_meter()`` zeroes it.
+
+    Evaluators: ``BalancedBinaryAccuracyEvaluator`` and ``LandmarkExpectedCoordiantesEvaluator`` in device-history mode
+    (``max_updates`` set): every replay appends one record to each.  Anything else is refused with ValueError, as are a model or
+    embedder in training mode and ``warmup < 1``.
+
+    ``warmup`` eager steps run first on the capture stream (they allocate the workspaces and the completion tickets there); their
+    records and their meter updates are rolled back on the device, so afterwards no evaluator holds a warm-up record and the meter
+    is where it was.  Parameter changes are honoured by RECAPTURE: the graph's kernels point at the model's folded BatchNorm
+    parameters and packed heads, which the model caches on in-place version counters; every call compares the version and address
+    of every parameter and buffer of both modules (and the model's cache entries) with the captured ones and captures again when
+    anything moved -- an optimizer step, ``load_state_dict``, a ``GraphedTrainStep`` replay, a train() / eval() round trip.
+    ``captures`` counts the captures."""
+
+    def __init__(self, model: Dict[str, torch.nn.Module], static_batch, criterion: Optional[Dict[str, object]], batch_size: int,
+                 use_coordinate_graph: bool = False, evaluators=None, warmup: int = 1):
+        from .evaluators import BalancedBinaryAccuracyEvaluator, LandmarkExpectedCoordiantesEvaluator
+        if warmup < 1:
+            raise ValueError("at least one eager warm-up step is needed (workspaces and completion tickets are created by it)")
+        for name in ("embedder", "landmark"):
+            if model[name].training:
+                raise ValueError(f"model[{name!r}] is in training mode: GraphedEvalStep captures an evaluation step (call .eval() first)")
+        evaluators = dict(evaluators or {})
+        for name, ev in evaluators.items():
+            if isinstance(ev, LandmarkExpectedCoordiantesEvaluator) and ev.max_updates is None:
+                raise ValueError(f"evaluator {name!r} is a host-mode LandmarkExpectedCoordiantesEvaluator, which reads its inputs back to "
+                                 "the host and cannot be captured: construct it with max_updates (evaluators.build(..., max_updates=N))")
+            if not isinstance(ev, (BalancedBinaryAccuracyEvaluator, LandmarkExpectedCoordiantesEvaluator)):
+                raise ValueError(f"evaluator {name!r} ({type(ev).__name__}) cannot be captured into a HIP graph")
+        if use_coordinate_graph and getattr(static_batch, "node_coords", None) is None:
+            raise ValueError("a coordinate-graph step needs static_batch.node_coords")
+        self.model, self.criterion, self.batch_size = model, criterion, int(batch_size)
+        self.use_coordinate_graph, self.evaluators, self.warmup = bool(use_coordinate_graph), evaluators, int(warmup)
+        self.static_batch = static_batch
+        device = static_batch.x.device
+        # the graph's own view of the batch: the caller's tensors, but node_coords through a private buffer the graph refills
+        self._batch = copy.copy(static_batch)
+        self._coords = None
+        if self.use_coordinate_graph:
+            self._coords = torch.empty_like(static_batch.node_coords)
+            self._batch.node_coords = self._coords
+        self._meter = torch.zeros(2, dtype=torch.float64, device=device)        # (sum of loss * batch size, count)
+        self._stream = torch.cuda.Stream(device=device)
+        self.captures = 0
+        self.graph = None
+        self.outputs = None
+        self._key = None
+        self._capture()
+
+    def _key_now(self):
+        lm = self.model["landmark"]
+        fold = lm.__dict__.get("_fold_cache", {})
+        return (_state_key(self.model["embedder"]), _state_key(lm), self.model["embedder"].training, lm.training,
+                tuple((k, id(v)) for k, v in fold.items()))
+
+    def _step(self):
+        if self._coords is not None:
+            self._coords.copy_(self.static_batch.node_coords)
+        preds, coord_preds, losses = eval_step(self.model, self._batch, self.criterion, self.batch_size, self.use_coordinate_graph,
+                                               self.evaluators)
+        if losses:
+            with torch.no_grad():
+                self._meter[0:1].add_(total_loss(losses).detach().reshape(1).to(torch.float64), alpha=self.batch_size)
+                self._meter[1:2].add_(self.batch_size)
+        return preds, coord_preds, losses
+
+    def _capture(self):
+        lm = self.model["landmark"]
+        graphed = getattr(lm, "use_hip_graph", False)
+        if graphed:
+            lm.use_hip_graph = False              # (the model's own replay would stand in for the kernels this graph has to hold)
+        try:
+            self.graph = None
+            self.outputs = None
+            meter = self._meter.clone()
+            stream = self._stream
+            stream.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(stream):
+                for _ in range(self.warmup):
+                    self._step()
+                # roll the warm-up back on the device: no evaluator keeps a warm-up record, the meter is where it was
+                self._meter.copy_(meter)
+                for ev in self.evaluators.values():
+                    counter = _record_counter(ev)
+                    if counter is not None:
+                        counter.sub_(self.warmup)
+                    if hasattr(ev, "_launched"):
+                        ev._launched = max(0, ev._launched - self.warmup)
+            torch.cuda.current_stream().wait_stream(stream)
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, stream=stream):
+                outputs = self._step()
+        finally:
+            if graphed:
+                lm.use_hip_graph = True
+        self.graph, self.outputs = graph, outputs
+        self.captures += 1
+        self._key = self._key_now()
+        # everything the captured kernels point at that the model caches (and may evict) stays alive with the graph
+        self._keep = (dict(lm.__dict__.get("_fold_cache", {})), dict(lm.__dict__.get("_kidsum", {})),
+                      list(getattr(getattr(lm, "_resolver", None), "_by_digest", {}).values()))
+
+    def __call__(self):
+        """Replay the step (recapturing first if the model's parameters or buffers moved); returns the static outputs."""
+        for name in ("embedder", "landmark"):
+            if self.model[name].training:
+                raise ValueError(f"model[{name!r}] is in training mode: call .eval() before evaluating")
+        if self._key_now() != self._key:
+            self._capture()
+        self.graph.replay()
+        return self.outputs
+
+    def loss_avg(self) -> float:
+        """The mean of the criteria's total over the evaluated frames since construction or reset_meter() (host read-back)."""
+        s, n = self._meter.tolist()
+        return s / n if n else 0.0
+
+    def reset_meter(self):
+        self._meter.zero_()
 
 
 @torch.no_grad()

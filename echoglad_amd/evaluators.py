@@ -39,17 +39,59 @@ def pixel_length(x0, y0, x1, y1, pix2mm_x, pix2mm_y):
     return torch.sqrt(((x0 - x1) * pix2mm_x) ** 2 + ((y0 - y1) * pix2mm_y) ** 2)
 
 
-class LandmarkExpectedCoordiantesEvaluator(object):
-    """Same constructor, methods and recorded numbers as the reference class (evaluators.py:237-617)."""
+def _host_or_device_table(name):
+    """A list-of-values table of the landmark evaluator: the host's own dictionary (host mode), or read back from the device history
+    when accessed (device mode, read-only)."""
+    def get(self):
+        if self.max_updates is None:
+            return self.__dict__["_" + name]
+        return self._tables()[name]
 
-    def __init__(self, logger, batch_size, frame_size, use_coord_graph):
+    def set(self, value):
+        if self.max_updates is not None:
+            raise AttributeError(f"{name} is read back from the device history in device mode (max_updates = {self.max_updates})")
+        self.__dict__["_" + name] = value
+    return property(get, set)
+
+
+class LandmarkExpectedCoordiantesEvaluator(object):
+    """Same constructor, methods and recorded numbers as the reference class (evaluators.py:237-617).
+
+    ``max_updates=None`` (host mode): the records are host lists, appended by ``update`` after three small read-backs.
+    ``max_updates=N`` (device mode): ``update`` appends one record -- coordinate errors, valid flags, width MAE / MPE and the per-frame
+    detail ``get_predictions`` returns -- to a device-side history of N records with two launches (heat-map models: the main grid's
+    decode and the record, csrc/heatmap.hip) or one (coordinate-graph models): no host synchronisation, no allocation, so an update
+    can be captured into a HIP graph (every replay appends a record).  The history is sized at construction on the current CUDA
+    device (an update on another device re-sizes it only while nothing has been recorded).  ``coordinate_errors``,
+    ``valid_errors``, ``width_MAE`` and ``width_MPE`` are read back when accessed, with the host mode's shape; ``compute``,
+    ``get_last``, ``get_sum_of_width_MAE / MPE`` and ``get_predictions`` read back once per call.  Past N the records are dropped
+    and reading raises.  ``pix2mm_x / pix2mm_y`` may be CPU tensors eagerly (copied into a device buffer); under a stream capture
+    they must be device tensors."""
+
+    coordinate_errors = _host_or_device_table("coordinate_errors")
+    valid_errors = _host_or_device_table("valid_errors")
+    width_MAE = _host_or_device_table("width_MAE")
+    width_MPE = _host_or_device_table("width_MPE")
+
+    def __init__(self, logger, batch_size, frame_size, use_coord_graph, max_updates=None):
+        if max_updates is not None and int(max_updates) < 1:
+            raise ValueError("max_updates must be >= 1 (or None: host mode)")
         self.batch_size = batch_size
         self.frame_size = frame_size
         self.use_coord_graph = use_coord_graph
+        self.max_updates = None if max_updates is None else int(max_updates)
+        self._state = None               # device mode: (device, history [N,16] f32, detail [N,B,24] f32, counter [1] i64, workspace, pix [2,B])
+        self._snapshot = None            # device mode: the tables of one read-back, while a method that reads them several times runs
         self.detailed_performance = {}
+        if self.max_updates is not None and torch.cuda.is_available():
+            self._allocate(torch.device("cuda", torch.cuda.current_device()))
         self.reset()
 
     def reset(self):
+        if self.max_updates is not None:
+            if self._state is not None:
+                self._state[3].zero_()
+            return
         self.coordinate_errors = {k: [] for k in ("ivs", "lvid_top", "lvid_bot", "lvpw")}
         self.valid_errors = {k: [] for k in ("ivs", "lvid_top", "lvid_bot", "lvpw")}
         self.width_MAE = {k: [] for k in ("lvid", "ivs", "lvpw")}
@@ -58,6 +100,8 @@ class LandmarkExpectedCoordiantesEvaluator(object):
 
     def update(self, y_pred, y_true, pix2mm_x, pix2mm_y, valid):
         """evaluators.py:291-391.  y_pred / y_true / valid: [B * nodes, 4] (device tensors are decoded on the device)."""
+        if self.max_updates is not None:
+            return self._update_device(y_pred, y_true, pix2mm_x, pix2mm_y, valid)
         self.detailed_performance.clear()
         B, F = self.batch_size, self.frame_size
         if self.use_coord_graph:
@@ -114,6 +158,10 @@ class LandmarkExpectedCoordiantesEvaluator(object):
 
     def compute(self):
         """evaluators.py:428-447: means over the recorded iterations, counting only iterations with a labelled landmark."""
+        with self._one_read_back():
+            return self._compute()
+
+    def _compute(self):
         def cnt(*keys):
             m = np.asarray(self.valid_errors[keys[0]])
             for k in keys[1:]:
@@ -137,14 +185,124 @@ class LandmarkExpectedCoordiantesEvaluator(object):
         return sum(v for k, v in t.items() if k in ("ivs_mpe", "lvid_mpe", "lvpw_mpe"))
 
     def get_last(self):
-        t = {k: self.coordinate_errors[k][-1] for k in NAMES}
-        for k in ("ivs", "lvid", "lvpw"):
-            t[k + "_w"] = self.width_MAE[k][-1]
-            t[k + "_mpe"] = self.width_MPE[k][-1]
-        return t
+        with self._one_read_back():
+            t = {k: self.coordinate_errors[k][-1] for k in NAMES}
+            for k in ("ivs", "lvid", "lvpw"):
+                t[k + "_w"] = self.width_MAE[k][-1]
+                t[k + "_mpe"] = self.width_MPE[k][-1]
+            return t
 
     def get_predictions(self):
-        return self.detailed_performance
+        if self.max_updates is None:
+            return self.detailed_performance
+        n = self._count()
+        if n == 0:
+            return {}
+        d = self._state[2][n - 1].cpu()                              # [B, 24]
+        preds, gt = d[:, 0:8].reshape(-1, 4, 2), d[:, 8:16].reshape(-1, 4, 2)
+        widths = {}
+        for tag, base in (("pred", 16), ("gt", 19)):
+            for j, k in enumerate(("ivs", "lvid", "lvpw")):
+                widths[f"{tag}_{k}_mm"] = d[:, base + j].clone()
+        coordinates = {"pred_ivs": preds[:, 3], "pred_lvid_top": preds[:, 0], "pred_lvid_bot": preds[:, 1], "pred_lvpw": preds[:, 2],
+                       "gt_ivs": gt[:, 3], "gt_lvid_top": gt[:, 0], "gt_lvid_bot": gt[:, 1], "gt_lvpw": gt[:, 2]}
+        return {"widths": widths, "coordinates": coordinates}
+
+    # ---- device mode --------------------------------------------------------------------------------------------------------------
+    def _allocate(self, device):
+        B, N = self.batch_size, self.max_updates
+        history = torch.zeros(N, ops.LANDMARK_RECORD_FLOATS, dtype=torch.float32, device=device)
+        detail = torch.zeros(N, B, ops.LANDMARK_DETAIL_FLOATS, dtype=torch.float32, device=device)
+        counter = torch.zeros(1, dtype=torch.int64, device=device)
+        workspace = None
+        if not self.use_coord_graph:
+            workspace = torch.empty(ops.landmark_record_workspace_bytes(B, self.frame_size), dtype=torch.uint8, device=device)
+        pix = torch.zeros(2, B, dtype=torch.float32, device=device)
+        self._state = (device, history, detail, counter, workspace, pix)
+
+    def _device_pix(self, t, k, device, capturing):
+        """pix2mm_x (k = 0) / pix2mm_y (k = 1) as a device float32 [B] tensor."""
+        B = self.batch_size
+        if t.numel() != B:
+            raise ValueError(f"pix2mm_{'xy'[k]} has {t.numel()} values but the evaluator's batch size is {B}")
+        if t.is_cuda:
+            if t.device != device:
+                raise ValueError(f"pix2mm_{'xy'[k]} is on {t.device}, the predictions on {device}")
+            return t.detach().reshape(B).to(torch.float32).contiguous()
+        if capturing:
+            raise ValueError(f"pix2mm_{'xy'[k]} is a CPU tensor: under a stream capture pix2mm_x / pix2mm_y must already be device "
+                             "tensors (a host-to-device copy cannot be part of the captured graph)")
+        buf = self._state[5][k]
+        buf.copy_(t.detach().reshape(B), non_blocking=True)
+        return buf
+
+    def _update_device(self, y_pred, y_true, pix2mm_x, pix2mm_y, valid):
+        B, F = self.batch_size, self.frame_size
+        if not y_pred.is_cuda:
+            raise RuntimeError("y_pred must be a CUDA (ROCm) tensor: the device-history mode has no CPU fallback")
+        capturing = torch.cuda.is_current_stream_capturing()
+        st = self._state
+        if st is None or st[0] != y_pred.device:
+            if capturing:
+                raise RuntimeError("the evaluator's device history is not allocated on the capturing device: update it once eagerly "
+                                   "in front of the capture")
+            if st is not None and int(st[3].item()):
+                raise RuntimeError(f"this evaluator records on {st[0]}: got predictions on {y_pred.device} (reset() first)")
+            self._allocate(y_pred.device)
+            st = self._state
+        dev, history, detail, counter, workspace, _ = st
+        px = self._device_pix(pix2mm_x, 0, dev, capturing)
+        py = self._device_pix(pix2mm_y, 1, dev, capturing)
+        if self.use_coord_graph:
+            cp = y_pred.detach().reshape(-1).to(torch.float32).contiguous()
+            cy = y_true.detach().reshape(-1).to(torch.float32).contiguous()
+            if cp.numel() != B * 8 or cy.numel() != B * 8:
+                raise ValueError(f"coordinate predictions / targets hold {cp.numel() // 8} / {cy.numel() // 8} frames of 4 (h, w) pairs "
+                                 f"but the evaluator's batch size is {B}")
+            ops.landmark_record_coord(cp, cy, B, px, py, history, detail, counter)
+            return
+        lg = y_pred.detach().reshape(-1, 4).to(torch.float32).contiguous()
+        if lg.shape[0] % B or lg.shape[0] // B < F * F:
+            raise ValueError(f"{lg.shape[0]} logit rows are not {B} frames holding a {F} x {F} main grid each "
+                             f"(the evaluator's batch size is {B})")
+        yy = y_true.detach().reshape(-1, 4).to(torch.float32).contiguous()
+        vv = valid.detach().reshape(-1, 4).to(torch.float32).contiguous()
+        ops.landmark_record_hm(lg, yy, vv, B, F, px, py, history, detail, counter, workspace)
+
+    def _count(self) -> int:
+        """Records appended since the last reset() (host read-back); raises past max_updates."""
+        if self._state is None:
+            return 0
+        n = int(self._state[3].item())
+        if n > self.max_updates:
+            raise RuntimeError(f"{n} updates since the last reset() but the history holds max_updates = {self.max_updates}: "
+                               "construct the evaluator with a larger max_updates")
+        return n
+
+    def _tables(self):
+        if self._snapshot is not None:
+            return self._snapshot
+        n = self._count()
+        h = self._state[1][:n].cpu().numpy() if n else np.zeros((0, ops.LANDMARK_RECORD_FLOATS), np.float32)
+        return {"coordinate_errors": {k: list(h[:, NAMES.index(k)]) for k in ("ivs", "lvid_top", "lvid_bot", "lvpw")},
+                "valid_errors": {k: [bool(v) for v in h[:, 4 + NAMES.index(k)] > 0] for k in ("ivs", "lvid_top", "lvid_bot", "lvpw")},
+                "width_MAE": {k: [float(v) for v in h[:, 8 + ("ivs", "lvid", "lvpw").index(k)]] for k in ("lvid", "ivs", "lvpw")},
+                "width_MPE": {k: [float(v) for v in h[:, 11 + ("ivs", "lvid", "lvpw").index(k)]] for k in ("lvid", "ivs", "lvpw")}}
+
+    def _one_read_back(self):
+        """Context: device mode reads the history back once for the whole block (host mode: nothing)."""
+        import contextlib
+        if self.max_updates is None or self._snapshot is not None:
+            return contextlib.nullcontext()
+
+        @contextlib.contextmanager
+        def snap():
+            self._snapshot = self._tables()
+            try:
+                yield
+            finally:
+                self._snapshot = None
+        return snap()
 
 
 LandmarkExpectedCoordinatesEvaluator = LandmarkExpectedCoordiantesEvaluator
@@ -246,9 +404,10 @@ class BalancedBinaryAccuracyEvaluator(object):
 _UNREACHABLE = ("accuracy", "mse", "landmarkerror")
 
 
-def build(eval_config, logger=None):
+def build(eval_config, logger=None, max_updates=None):
     """src/builders/evaluator_builder.py: {standard: evaluator} for ``eval_config['standards']``.  The keys ``batch_size``,
-    ``frame_size`` and ``use_coordinate_graph`` configure the landmark evaluator."""
+    ``frame_size`` and ``use_coordinate_graph`` configure the landmark evaluator; ``max_updates`` (None: host mode) selects its
+    device-history mode with that many records (``GraphedEvalStep`` captures only that mode)."""
     standards = list(eval_config["standards"])
     batch_size, frame_size = eval_config["batch_size"], eval_config["frame_size"]
     use_coord_graph = eval_config["use_coordinate_graph"]
@@ -258,7 +417,8 @@ def build(eval_config, logger=None):
             evaluators[standard] = BalancedBinaryAccuracyEvaluator(logger=logger)
         elif standard == "landmarkcoorderror":
             evaluators[standard] = LandmarkExpectedCoordiantesEvaluator(logger=logger, batch_size=batch_size,
-                                                                        frame_size=frame_size, use_coord_graph=use_coord_graph)
+                                                                        frame_size=frame_size, use_coord_graph=use_coord_graph,
+                                                                        max_updates=max_updates)
         elif standard in _UNREACHABLE:
             raise NotImplementedError(f"evaluator {standard!r} is not implemented: its update(y_pred, y_true) takes two arguments and "
                                       "the reference's engine calls every evaluator with three or five (src/engine.py:492), so the "

@@ -1081,6 +1081,65 @@ def confusion_counts(pred: torch.Tensor, y: torch.Tensor, valid: torch.Tensor, h
                                                _ptr(history), history.shape[0], _ptr(counter), stream), "eg_confusion_counts")
 
 
+LANDMARK_RECORD_FLOATS = 16         # eg_landmark_record_*: one record of the history
+LANDMARK_DETAIL_FLOATS = 24         # ... and one frame of its detail block
+
+
+def landmark_record_workspace_bytes(batch: int, frame: int) -> int:
+    return int(_lib.load().eg_landmark_record_workspace_bytes(int(batch), int(frame)))
+
+
+def _check_record_buffers(device, batch: int, pix2mm_x, pix2mm_y, history, detail, counter) -> None:
+    for name, t in (("pix2mm_x", pix2mm_x), ("pix2mm_y", pix2mm_y), ("history", history), ("detail", detail), ("counter", counter)):
+        if not t.is_cuda or t.device != device:
+            raise RuntimeError(f"{name} must be a CUDA (ROCm) tensor on {device}: the HIP path has no CPU fallback")
+        if not t.is_contiguous():
+            raise RuntimeError(f"{name} must be contiguous")
+    for name, t in (("pix2mm_x", pix2mm_x), ("pix2mm_y", pix2mm_y)):
+        if t.dtype != torch.float32 or t.numel() != batch:
+            raise RuntimeError(f"{name} must be float32 with one value per frame ({batch}), got {tuple(t.shape)} {t.dtype}")
+    if history.dtype != torch.float32 or history.dim() != 2 or history.shape[1] != LANDMARK_RECORD_FLOATS or history.shape[0] < 1:
+        raise RuntimeError(f"history must be float32 [capacity, {LANDMARK_RECORD_FLOATS}], got {tuple(history.shape)} {history.dtype}")
+    if detail.dtype != torch.float32 or tuple(detail.shape) != (history.shape[0], batch, LANDMARK_DETAIL_FLOATS):
+        raise RuntimeError(f"detail must be float32 [{history.shape[0]}, {batch}, {LANDMARK_DETAIL_FLOATS}], got {tuple(detail.shape)}")
+    if counter.dtype != torch.int64 or counter.numel() != 1:
+        raise RuntimeError("counter must be one int64 element")
+
+
+def landmark_record_hm(logits, labels, valid, batch: int, frame: int, pix2mm_x, pix2mm_y, history, detail, counter, workspace) -> None:
+    """Append one landmark-evaluator record (the main grid's decode -> coordinate errors, valid flags, width MAE / MPE, per-frame
+    detail) of a heat-map model to ``history[counter]`` / ``detail[counter]`` and advance ``counter`` -- two launches on the current
+    stream (eg_landmark_record_hm), no host synchronisation, no allocation.  logits / labels / valid: contiguous CUDA float32
+    [batch * n_rows, 4]; pix2mm_x / pix2mm_y: CUDA float32 [batch]; history float32 [capacity, 16]; detail float32
+    [capacity, batch, 24]; counter int64 [1]; workspace: uint8, ``landmark_record_workspace_bytes(batch, frame)`` bytes or more,
+    not shared with another stream's launch.  Past capacity nothing is written but the counter still advances."""
+    if logits.shape[0] % batch:
+        raise RuntimeError(f"{logits.shape[0]} logit rows is not a multiple of the batch size {batch}")
+    _check_logits(logits, "logits")
+    for name, t in (("labels", labels), ("valid", valid)):
+        _check_logits(t, name, logits.shape[0])
+    _check_record_buffers(logits.device, batch, pix2mm_x, pix2mm_y, history, detail, counter)
+    if workspace.device != logits.device or workspace.dtype != torch.uint8:
+        raise RuntimeError("workspace must be a uint8 CUDA tensor on the logits' device")
+    stream = _stream(logits)
+    _lib.check(_lib.load().eg_landmark_record_hm(_ptr(logits), _ptr(labels), _ptr(valid), batch, logits.shape[0] // batch, frame,
+                                                 _ptr(pix2mm_x), _ptr(pix2mm_y), _ptr(workspace), workspace.numel(), _ptr(history),
+                                                 _ptr(detail), history.shape[0], _ptr(counter), stream), "eg_landmark_record_hm")
+
+
+def landmark_record_coord(coord_pred, coord_y, batch: int, pix2mm_x, pix2mm_y, history, detail, counter) -> None:
+    """landmark_record_hm for a coordinate-graph model: the record from the predicted and labelled (h, w) of the 4 landmarks of every
+    frame (contiguous CUDA float32 [batch * 4, 2]), every landmark valid -- one launch (eg_landmark_record_coord)."""
+    for name, t in (("coord_pred", coord_pred), ("coord_y", coord_y)):
+        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != batch * 8:
+            raise RuntimeError(f"{name} must be a contiguous CUDA float32 tensor of {batch} x 4 (h, w) pairs, got {tuple(t.shape)} {t.dtype}")
+    _check_record_buffers(coord_pred.device, batch, pix2mm_x, pix2mm_y, history, detail, counter)
+    stream = _stream(coord_pred)
+    _lib.check(_lib.load().eg_landmark_record_coord(_ptr(coord_pred), _ptr(coord_y), batch, _ptr(pix2mm_x), _ptr(pix2mm_y),
+                                                    _ptr(history), _ptr(detail), history.shape[0], _ptr(counter), stream),
+               "eg_landmark_record_coord")
+
+
 class _CriteriaFn(torch.autograd.Function):
     """WeightedBCEWithLogitsLoss or WeightedBCE + ExpectedLandmarkMSE (+ MSE or MAE on the landmark coordinates) of one training step
     as ONE autograd node over eg_criteria_ex_fwd / eg_criteria_ex_bwd: (logits [B*n,4], coord_pred [R,2] | None) -> (total, bce, elm,

@@ -85,8 +85,9 @@ extern "C" {
  * 134: eg_dropout_epoch_add / _set, eg_debug_dropout_epoch (round 5: a whole train step as one HIP graph).
  * 135: eg_gcn_layer_bwd_lower, eg_bilinear4_bwd_rows_sums, eg_avg_pool_pyramid_fwd / _bwd, eg_criteria_* (round 6).
  * 136: eg_classifier_train_fwd_act(h_sparse), eg_classifier_bwd_sums(layer_residual, recompute_h).  137, 138: eg_coord_update_fwd / _bwd.  139, 140: eg_adam_step.
- * 141: eg_confusion_counts.  142: eg_bce_probs_fwd / _bwd, eg_criteria_ex_fwd / _bwd. */
-#define EG_ABI_VERSION 142
+ * 141: eg_confusion_counts.  142: eg_bce_probs_fwd / _bwd, eg_criteria_ex_fwd / _bwd.
+ * 143: eg_landmark_record_workspace_bytes, eg_landmark_record_hm, eg_landmark_record_coord. */
+#define EG_ABI_VERSION 143
 
 #define EG_CHANNELS 128 /* node_embedding_dim == node_hidden_dim (configs/default.yml:13-14) */
 
@@ -613,6 +614,34 @@ int eg_criteria_ex_bwd(const float* logits, const float* labels, const float* va
  * EG_ERR_UNSUPPORTED for channels outside 1..8, EG_ERR_ARG for a NULL buffer or misaligned 64-bit buffer; nothing launched then. */
 int eg_confusion_counts(const float* pred, const float* y, const float* valid, int64_t rows, int channels, void* workspace,
                         size_t workspace_bytes, int64_t* history, int64_t capacity, int64_t* counter, eg_stream_t stream);
+
+/* ---- landmark-evaluator records (reference: LandmarkExpectedCoordiantesEvaluator.update, src/core/evaluators.py:291-391) -----
+ * One update appends ONE record to a device-side history and advances *counter (a device int64) by one: a launch sequence
+ * captured into a HIP graph appends one record per replay.  Record k = *counter (history: [capacity][16] f32):
+ *   [0..3]   coordinate errors of lvid_top, lvid_bot, lvpw, ivs (sum over the frames of err * vs, divided by nv)
+ *   [4..7]   valid flags of the same landmarks (1.0 iff nv > 0 before a zero nv became 1)
+ *   [8..10]  width MAE of ivs, lvid, lvpw;  [11..13] width MPE of ivs, lvid, lvpw;  [14..15] 0
+ * and its per-frame detail block (detail: [capacity][batch][24] f32): pred (h, w) of the 4 landmarks [0..7], gt (h, w) [8..15],
+ * pred widths in mm {ivs, lvid, lvpw} [16..18], gt widths [19..21], 0 [22..23].  vs = the per-(frame, landmark) mean of valid,
+ * nv = its sum over the frames.  fp32 in the host class's operation order without FMA contraction, sums over the frames in
+ * ascending order: bit-reproducible; a landmark without a valid row and a zero ground-truth width give the host's IEEE results.
+ * With k >= capacity nothing is written but *counter still advances (the reader detects the overflow).  pix2mm_x / pix2mm_y:
+ * [batch] f32 device arrays.  No allocation, no memset, no host synchronisation.
+ * eg_landmark_record_hm: heat-map models.  logits / labels / valid [batch * n_rows, 4] f32 (16-byte aligned); the main grid is
+ *   the last frame * frame rows of every frame: softmax-expected (h, w), the label's (h, w) and vs as eg_heatmap_expect_fwd
+ *   decodes them.  TWO launches; the last workgroup of the second computes the record.  workspace: device memory of at least
+ *   eg_landmark_record_workspace_bytes(batch, frame) bytes (8-byte aligned), not shared with a launch in flight on another
+ *   stream.  The completion ticket is a word per (device, stream) allocated at the first launch on a stream: make that first
+ *   launch outside a stream capture.
+ * eg_landmark_record_coord: coordinate-graph models.  coord_pred / coord_y [batch * 4, 2] f32 (h, w); every landmark counts as
+ *   valid (vs = 1).  ONE launch, no workspace.
+ * EG_ERR_ARG for a NULL or misaligned buffer, a main grid larger than the frame's rows or a short workspace; nothing launched then. */
+size_t eg_landmark_record_workspace_bytes(int batch, int frame);
+int eg_landmark_record_hm(const float* logits, const float* labels, const float* valid, int batch, int64_t n_rows, int frame,
+                          const float* pix2mm_x, const float* pix2mm_y, void* workspace, size_t workspace_bytes, float* history,
+                          float* detail, int64_t capacity, int64_t* counter, eg_stream_t stream);
+int eg_landmark_record_coord(const float* coord_pred, const float* coord_y, int batch, const float* pix2mm_x, const float* pix2mm_y,
+                             float* history, float* detail, int64_t capacity, int64_t* counter, eg_stream_t stream);
 
 /* ---- node-feature packing (the step right before the hot path) -------------------------------------------
  * Reference: the per-sample loops at the tail of create_node_pixels (src/core/models.py:498-537, :590-636,
