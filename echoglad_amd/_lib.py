@@ -1,5 +1,9 @@
 """ctypes binding of the C-ABI library (include/echoglad_hip.h).
 
+The ctypes signature of every entry point is read from the header when this module is imported: the header is the
+ABI contract, and a table written out a second time by hand can disagree with it in a type or in the order of two
+arguments without anything noticing.
+
 There is no CPU fallback: if the shared object is missing or does not load,
 ``load()`` raises and every op that needs it fails loudly."""
 from __future__ import annotations
@@ -8,20 +12,20 @@ import ctypes as ct
 import os
 import re
 from pathlib import Path
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Tuple
 
 _PKG = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("ECHOGLAD_LIB", _PKG / "lib" / "libechoglad_hip.so"))
 HEADER_PATH = _PKG.parent / "include" / "echoglad_hip.h"
 
 EG_OK, EG_ERR_ARG, EG_ERR_UNSUPPORTED, EG_ERR_HIP = 0, -1, -2, -3
-ABI_VERSION = 143          # EG_ABI_VERSION of include/echoglad_hip.h that SIGNATURES below was written for
+# EG_ABI_VERSION of the include/echoglad_hip.h that the structures below and the wrappers' argument order were written for
+ABI_VERSION = 143
 
 _lib: Optional[ct.CDLL] = None
 
 _p = ct.c_void_p
-_i = ct.c_int
-_i64 = ct.c_int64
+
 
 class ClsTrainParams(ct.Structure):
     """eg_cls_train_params of include/echoglad_hip.h (stacked parameters of the 4 classifier heads, train mode)."""
@@ -31,119 +35,87 @@ class ClsTrainParams(ct.Structure):
                [("seed1", ct.c_uint64), ("seed2", ct.c_uint64)]
 
 
-_f = ct.c_float
-_u64 = ct.c_uint64
-_pp = ct.POINTER(ClsTrainParams)
-
-
 class LowerSums(ct.Structure):
     """eg_lower_sums: the layer below the one whose dX launch takes its BatchNorm-backward sums (eg_gcn_layer_bwd_lower)."""
-    _fields_ = [("z", _p), ("bn", _p), ("relu", _i), ("dropout_p", _f), ("seed", _u64), ("row_hi", _i64), ("tile_scratch", _p),
-                ("sums_out", _p)]
+    _fields_ = [("z", _p), ("bn", _p), ("relu", ct.c_int), ("dropout_p", ct.c_float), ("seed", ct.c_uint64),
+                ("row_hi", ct.c_int64), ("tile_scratch", _p), ("sums_out", _p)]
 
 
 class GivenSums(ct.Structure):
     """eg_given_sums: sums of THIS layer that somebody else has taken already (+ the bilinear backward's later additions)."""
-    _fields_ = [("sums", _p), ("frames", _i), ("row_lo", _i64), ("n_valid", _i64), ("taps", _p)]
+    _fields_ = [("sums", _p), ("frames", ct.c_int), ("row_lo", ct.c_int64), ("n_valid", ct.c_int64), ("taps", _p)]
 
 
-# name -> (restype, argtypes); must list every symbol the header declares
-SIGNATURES: Dict[str, tuple] = {
-    "eg_version": (_i, []),
-    "eg_last_error": (ct.c_char_p, []),
-    "eg_topo_create": (_i, [_i, _i, _i, _i, _i, _i, _i, ct.POINTER(_p)]),
-    "eg_csr_create": (_i, [_p, _i64, _i64, _p, ct.POINTER(_p)]),
-    "eg_graph_is_symmetric": (_i, [_p]),
-    "eg_csr_create_transposed": (_i, [_p, _p, _i64, _p, ct.POINTER(_p)]),
-    "eg_graph_destroy": (_i, [_p]),
-    "eg_graph_num_nodes": (_i64, [_p]),
-    "eg_graph_is_structured": (_i, [_p]),
-    "eg_graph_num_tiles": (_i64, [_p]),
-    "eg_graph_deg_inv_sqrt": (_i, [_p, _p, _p]),
-    "eg_edge_hash": (_i, [_p, _i64, _p, _p]),
-    "eg_debug_xcc": (_i, [_p, _i, _p]),
-    "eg_dropout_epoch_add": (_i, [ct.c_uint64, _p]),
-    "eg_dropout_epoch_set": (_i, [ct.c_uint64, _p]),
-    "eg_debug_dropout_epoch": (_i, [ct.POINTER(ct.c_uint64)]),
-    "eg_debug_layer_timing_begin": (_i, [_i]),
-    "eg_debug_layer_timing_end": (_i, [ct.POINTER(ct.c_float), ct.POINTER(ct.c_int), _i]),
-    "eg_debug_phase_cycles": (_i, [_p, ct.POINTER(ct.c_uint64), _i]),
-    "eg_gcn_layer_fwd": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _p, _p]),
-    "eg_graph_kidsum_rows": (_i64, [_p]),
-    "eg_graph_fused_classifier_ok": (_i, [_p]),
-    "eg_gcn_layer_fwd_chain": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p]),
-    "eg_gcn_layer_cls_fwd": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p]),
-    "eg_gcn_layer_fwd_jk": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p]),
-    "eg_graph_ps_launches": (ct.c_uint, [_p]),
-    "eg_graph_layer_launches": (ct.c_uint, [_p]),
-    "eg_gcn_aggregate": (_i, [_p, _i, _p, _p, _p]),
-    "eg_linear128_fwd": (_i, [_p, _i64, _p, _p, _p, _p, _i, _i, _p, _p]),
-    "eg_classifier_fwd": (_i, [_p, _i, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p]),
-    "eg_workspace_bytes": (ct.c_size_t, []),
-    "eg_colsum128": (_i, [_p, _i64, _p, _p, _p]),
-    "eg_dweight128": (_i, [_p, _p, _i64, _p, _p, _p]),
-    "eg_bn_stats": (_i, [_p, _i64, _p, _p, _p, _p]),
-    "eg_bn_act_fwd": (_i, [_p, _i64, _p, _p, _p, _i, ct.c_float, ct.c_uint64, _p, _p]),
-    "eg_bn_act_fwd_tiles": (_i, [_p, _i, _p, _p, _p, _p, _i, ct.c_float, ct.c_uint64, _p, _p, _p]),
-    "eg_bn_act_bwd": (_i, [_p, _p, _i64, _p, _p, _p, _p, _i, ct.c_float, ct.c_uint64, _p, _p, _p, _p, _p]),
-    "eg_gcn_layer_train_fwd": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _f, _f, _i, _f, _u64, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
-    "eg_gcn_layer_bwd": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _f, _u64, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
-    "eg_classifier_train_workspace_bytes": (ct.c_size_t, []),
-    "eg_classifier_train_fwd": (_i, [_p, _i, _i64, _i64, _i64, _pp, _p, _p, _p, _p, _i, _p, _p]),
-    "eg_classifier_train_fwd_act": (_i, [_p, _p, _p, _i, _f, _u64, _p, _i, _i64, _i64, _i64, _pp, _p, _p, _p, _p, _i, _p, _i, _p]),
-    "eg_classifier_bwd": (_i, [_p, _p, _i, _i64, _i64, _i64, _pp, _p, _p, _p, _p, _p, _p, _p, _p]),
-    "eg_classifier_bwd_sums": (_i, [_p, _p, _i, _i64, _i64, _i64, _pp, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _f, _u64, _p, _p, _i, _p]),
-    "eg_gcn_layer_bwd_presummed": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _f, _u64, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i,
-                                        _i64, _i64, _p]),
-    "eg_gcn_layer_bwd_lower": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _f, _u64, _i, _p, _p, _p, _p, _p, _p, _p,
-                                    ct.POINTER(GivenSums), ct.POINTER(LowerSums), _p]),
-    "eg_bilinear4_bwd_rows_sums": (_i, [_p, _i64, _p, _p, _i, _i, _i64, _i64, _i, _p, _p, ct.POINTER(LowerSums), _p, _p]),
-    "eg_coord_mlp_fwd": (_i, [_p, _p, _i, _pp, _i, _i, _p, _p, _p, _p, _p, _p]),
-    "eg_coord_mlp_bwd": (_i, [_p, _p, _p, _i, _pp, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
-    "eg_coord_mlp_fwd_rows": (_i, [_p, _i64, _p, _p, _i, _pp, _i, _i, _p, _p, _p, _p, _p, _p]),
-    "eg_coord_mlp_bwd_rows": (_i, [_p, _p, _p, _i, _pp, _i, _p, _p, _p, _p, _p, _p, _i64, _i, _p, _p, _p]),
-    "eg_adam_step": (_i, [_p, _i, _p, ct.c_float, _p, ct.c_float, ct.c_float, ct.c_float, ct.c_float, _i, _p]),
-    "eg_coord_update_fwd": (_i, [_p, _i64, _i64, _i64, _p, _i, _pp, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
-    "eg_coord_update_bwd": (_i, [_p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _i, _pp, _i, _p, _p, _p, _p, _p, _p, ct.POINTER(LowerSums), _p, _p, _p, _p]),
-    "eg_bilinear4_fwd_rows": (_i, [_p, _p, _i, _i, _i64, _i64, _i, _p, _i64, _p]),
-    "eg_bilinear4_bwd_rows": (_i, [_p, _i64, _p, _p, _i, _i, _i64, _i64, _i, _p, _p, _p]),
-    "eg_bilinear4_fwd": (_i, [_p, _p, _i, _i, _i64, _i64, _i, _p, _p]),
-    "eg_bilinear4_bwd": (_i, [_p, _p, _p, _i, _i, _i64, _i64, _i, _p, _p, _p]),
-    "eg_pack_levels": (_i, [ct.POINTER(_p), ct.POINTER(_i), _i, _i, _i64, _i64, _p, _p]),
-    "eg_conv1x1_relu_pack_levels": (_i, [ct.POINTER(_p), ct.POINTER(_p), ct.POINTER(_p), ct.POINTER(_i), ct.POINTER(_i), _i, _i,
-                                         _i64, _i64, _p, _p]),
-    "eg_avg_pool_pyramid_fwd": (_i, [_p, _i64, _i, ct.POINTER(_i), _i, ct.POINTER(_p), _p]),
-    "eg_avg_pool_pyramid_bwd": (_i, [ct.POINTER(_p), _p, _i64, _i, ct.POINTER(_i), _i, _p, _p]),
-    "eg_unpack_levels": (_i, [_p, ct.POINTER(_p), ct.POINTER(_i), _i, _i, _i64, _i64, _p]),
-    "eg_heatmap_workspace_bytes": (ct.c_size_t, [_i, ct.POINTER(_i), _i]),
-    "eg_heatmap_expect_fwd": (_i, [_p, _p, _p, _i, _i64, ct.POINTER(_i), ct.POINTER(_i), _i, _p, _p, _p, _p, _p, _p, _p]),
-    "eg_heatmap_expect_bwd": (_i, [_p, _p, _p, _p, _i, _i64, ct.POINTER(_i), ct.POINTER(_i), _i, _p, _p]),
-    "eg_criteria_workspace_bytes": (ct.c_size_t, [_i, ct.POINTER(_i), _i]),
-    "eg_criteria_fwd": (_i, [_p, _p, _p, _i, _i64, ct.POINTER(_i), ct.POINTER(_i), _i, _p, _f, _f, _f, _p, _p, _i64, _f, _p, _p, _p, _p,
-                             _p, _p, _p, _p, _p, _p, _p]),
-    "eg_criteria_bwd": (_i, [_p, _p, _p, _i, _i64, ct.POINTER(_i), ct.POINTER(_i), _i, _f, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p,
-                             _p, _p, _p]),
-    "eg_criteria_ex_fwd": (_i, [_p, _p, _p, _i, _i64, ct.POINTER(_i), ct.POINTER(_i), _i, _p, _f, _f, _f, _p, _p, _i64, _f, _p, _p, _p,
-                                _p, _p, _p, _p, _p, _p, _p, _i, _i, _p]),
-    "eg_criteria_ex_bwd": (_i, [_p, _p, _p, _i, _i64, ct.POINTER(_i), ct.POINTER(_i), _i, _f, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p,
-                                _p, _p, _i, _i, _p]),
-    "eg_elm_reduce": (_i, [_p, _p, _p, _p, _i, _i, ct.c_float, _p, _p, _p]),
-    "eg_bce_logits_fwd": (_i, [_p, _p, _p, _i64, ct.c_float, _p, _p, _p]),
-    "eg_bce_logits_bwd": (_i, [_p, _p, _p, _i64, ct.c_float, _p, _p, _p]),
-    "eg_bce_probs_fwd": (_i, [_p, _p, _p, _i64, ct.c_float, _p, _p, _p]),
-    "eg_bce_probs_bwd": (_i, [_p, _p, _p, _i64, ct.c_float, _p, _p, _p]),
-    "eg_confusion_counts": (_i, [_p, _p, _p, _i64, _i, _p, ct.c_size_t, _p, _i64, _p, _p]),
-    "eg_landmark_record_workspace_bytes": (ct.c_size_t, [_i, _i]),
-    "eg_landmark_record_hm": (_i, [_p, _p, _p, _i, _i64, _i, _p, _p, _p, ct.c_size_t, _p, _p, _i64, _p, _p]),
-    "eg_landmark_record_coord": (_i, [_p, _p, _i, _p, _p, _p, _p, _i64, _p, _p]),
-}
+# ---------------------------------------------------------------------------
+# the header -> name -> (restype, argtypes)
+# ---------------------------------------------------------------------------
+_SCALARS = {"int": ct.c_int, "int64_t": ct.c_int64, "uint64_t": ct.c_uint64, "float": ct.c_float, "size_t": ct.c_size_t,
+            "unsigned": ct.c_uint}
+_STRUCTS = {"eg_cls_train_params": ClsTrainParams, "eg_lower_sums": LowerSums, "eg_given_sums": GivenSums}
+# what a pointer that is passed as an address (c_void_p takes tensors' addresses, ctypes arrays and byref(...)) may point to
+_POINTEES = set(_SCALARS) | {"void", "char", "double", "eg_graph", "eg_adam_tensor"}
+_DECLARATION = re.compile(r"([A-Za-z_][\w \t\n\*]*?)\b(eg_[a-z0-9_]+)\s*\(([^()]*)\)\s*;")
+
+
+def _ctype(text: str, entry: str, is_param: bool):
+    """The ctypes type of one C type as the header spells it (a parameter together with its name, or a return type)."""
+    if "[" in text or "]" in text:
+        raise RuntimeError(f"{entry}: array parameter '{' '.join(text.split())}' has no ctypes mapping: declare it as a pointer")
+    words = [w for w in text.replace("*", " * ").split() if w != "const"]
+    stars = words.count("*")
+    words = [w for w in words if w != "*"]
+    if is_param and len(words) > 1:
+        words = words[:-1]                                  # the parameter's name
+    base = " ".join(words)
+    if stars == 0 and base in _SCALARS:
+        return _SCALARS[base]
+    if stars == 0 and base == "eg_stream_t":
+        return ct.c_void_p
+    if stars == 1 and base in _STRUCTS:
+        return ct.POINTER(_STRUCTS[base])
+    if stars == 1 and base == "char" and not is_param:
+        return ct.c_char_p
+    if stars >= 1 and base in _POINTEES and is_param:
+        return ct.c_void_p
+    raise RuntimeError(f"{entry}: no ctypes mapping for '{' '.join(text.split())}' (echoglad_amd/_lib.py reads its signatures "
+                       f"from {HEADER_PATH.name})")
+
+
+def parse_header(text: str) -> Dict[str, Tuple[object, list, bool]]:
+    """name -> (restype, argtypes, last parameter is the stream) of every function a C header in the style of
+    include/echoglad_hip.h declares.  A type with no ctypes mapping raises with the entry point's name."""
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    text = re.sub(r"^[ \t]*#[^\n]*", "", text, flags=re.M)                       # preprocessor lines
+    text = text.replace('extern "C" {', "")
+    text = re.sub(r"typedef\s+struct\s+\w+\s*\{[^{}]*\}\s*\w+\s*;", "", text)   # field layouts: the ct.Structure classes
+    table = {}
+    for m in _DECLARATION.finditer(text):
+        ret, name, params = m.group(1), m.group(2), m.group(3).strip()
+        params = [] if params in ("", "void") else [p.strip() for p in params.split(",")]
+        if name in table:
+            raise RuntimeError(f"{name} is declared twice")
+        table[name] = (_ctype(ret, name, False), [_ctype(p, name, True) for p in params],
+                       bool(params) and params[-1].split()[0] == "eg_stream_t")
+    return table
+
+
+def _read_header() -> str:
+    try:
+        return HEADER_PATH.read_text()
+    except OSError as e:
+        raise RuntimeError(f"{HEADER_PATH} cannot be read ({e}): the binding takes every entry point's signature from it") from e
+
+
+_PARSED = parse_header(_read_header())
+# name -> (restype, argtypes) of every symbol the header declares
+SIGNATURES: Dict[str, tuple] = {name: (res, args) for name, (res, args, _) in _PARSED.items()}
+TAKES_STREAM = frozenset(name for name, d in _PARSED.items() if d[2])        # ... and those whose last argument is the stream
 
 
 def header_symbols() -> List[str]:
     """Every function name declared in include/echoglad_hip.h."""
-    text = HEADER_PATH.read_text()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(eg_[a-z0-9_]+)\s*\(", text)))
+    return sorted(SIGNATURES)
 
 
 def load() -> ct.CDLL:
@@ -159,8 +131,7 @@ def load() -> ct.CDLL:
     lib = ct.CDLL(str(LIB_PATH), mode=ct.RTLD_GLOBAL if hasattr(ct, "RTLD_GLOBAL") else 0)
     # a library built from other sources than this binding would take the calls below with shifted arguments: refuse it
     try:
-        lib.eg_version.restype = _i
-        lib.eg_version.argtypes = []
+        lib.eg_version.restype, lib.eg_version.argtypes = SIGNATURES["eg_version"]
         got = int(lib.eg_version())
     except AttributeError:
         got = None

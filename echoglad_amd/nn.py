@@ -1185,8 +1185,7 @@ class HierarchicalPatchModel(nn.Module):
     def _train_kidsums(self, graph: ops.Graph, gb: int):
         """Child-sum side buffers of the chained train forward (layer i leaves the child sums of its output for layer i + 1:
         eg_gcn_layer_train_fwd), or (None, None)."""
-        if graph.kidsum_rows == 0 or self.num_gnn_layers < 2 or not ROUTES.train_chain or \
-                not ops.train_chain_supported():
+        if graph.kidsum_rows == 0 or self.num_gnn_layers < 2 or not ROUTES.train_chain:
             return None, None
         return self._kidsum_buffers(graph, gb)
 

@@ -1,0 +1,21 @@
+"""Thin Python wrappers over the C-ABI (no compute here; pointers + stream only).
+
+Every function enqueues on ``torch.cuda.current_stream()`` and returns torch
+tensors that own the output memory.  Inputs must be CUDA fp32 contiguous
+``[rows, 128]``.
+
+One module per family of entry points; ``_core`` holds what they share (the call into the library, the argument checker,
+the scratch cache).  Everything public is re-exported here: ``from echoglad_amd import ops; ops.gcn_layer_fwd(...)``."""
+from ._core import C, _level_arrays, _ptr, _stream                                         # noqa: F401  (_*: tests' raw ABI calls)
+from .graph import LAUNCH_KINDS, Graph, dropout_epoch, dropout_epoch_add, dropout_epoch_set, edge_hash, layer_timing   # noqa: F401
+from .infer import classifier_fwd, gcn_aggregate, gcn_layer_cls_fwd, gcn_layer_fwd, linear128_fwd, new_kidsum          # noqa: F401
+from .train import (CLS_GRADS_FLOATS, bn_act_bwd, bn_act_fwd, bn_act_fwd_tiles, bn_stats, classifier_bwd,             # noqa: F401
+                    classifier_layer_sums_supported, classifier_recompute_h_supported, classifier_train_fwd,
+                    classifier_train_fwd_act, colsum128, dweight128, gcn_layer_bwd, gcn_layer_train_fwd, lower_sums_supported)
+from .coord import (COORD_MLP_GRADS_FLOATS, bilinear4, bilinear4_bwd, bilinear4_fwd, coord_mlp_bwd, coord_mlp_fwd,     # noqa: F401
+                    coord_update_bwd, coord_update_fwd, scatter_coord_rows)
+from .criteria import (CONFUSION_MAX_CHANNELS, CONFUSION_WORKSPACE_BYTES, LANDMARK_DETAIL_FLOATS, LANDMARK_RECORD_FLOATS,   # noqa: F401
+                       bce_logits, bce_logits_fwd, bce_probs, bce_probs_fwd, confusion_counts, elm_reduce, heatmap_expect,
+                       heatmap_expect_bwd, heatmap_expect_fwd, landmark_criteria, landmark_record_coord, landmark_record_hm,
+                       landmark_record_workspace_bytes)
+from .pack import avg_pool_pyramid, conv1x1_relu_pack_levels, pack_levels, pyramid_pack, pyramid_supported             # noqa: F401

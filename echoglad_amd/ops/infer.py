@@ -1,0 +1,111 @@
+"""Inference layers and heads: the fused GCN layer in its plain / chained / running-maximum forms, the layer with the
+classifier heads folded in, and the pieces they are made of."""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+
+from ._core import C, _check, _check_rows, _check_vec, call
+from .graph import Graph
+
+_HEAD_KEYS = ("w1", "s1", "t1", "w2", "s2", "t2", "w3", "b3")       # the packed inference parameters of the 4 heads, in call order
+
+
+def _check_layer_args(rows: int, x, weight, scale, shift, residual) -> None:
+    _check_rows(x, "x", rows)
+    _check(weight, "weight", (C, C))
+    _check_vec(scale, "scale", C)
+    _check_vec(shift, "shift", C)
+    _check_rows(residual, "residual", rows, optional=True)
+
+
+def gcn_layer_fwd(graph: Graph, batch: int, x: torch.Tensor, weight: torch.Tensor,
+                  scale: Optional[torch.Tensor] = None, shift: Optional[torch.Tensor] = None,
+                  residual: Optional[torch.Tensor] = None, relu: bool = False, transpose_w: bool = False,
+                  out: Optional[torch.Tensor] = None, kidsum_in: Optional[torch.Tensor] = None,
+                  kidsum_out: Optional[torch.Tensor] = None, jk_in: Optional[torch.Tensor] = None,
+                  jk_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """act((A_hat x) W^T * scale + shift) + residual in one kernel.
+
+    kidsum_in / kidsum_out: child-sum side buffers of a chained stack of layers (see `new_kidsum`,
+    include/echoglad_hip.h eg_gcn_layer_fwd_chain).  jk_in / jk_out: running JumpingKnowledge('max') maximum,
+    jk_out = max(jk_in, result) (eg_gcn_layer_fwd_jk; the first layer passes x as jk_in)."""
+    rows = graph.num_nodes * batch
+    _check_layer_args(rows, x, weight, scale, shift, residual)
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _check_rows(out, "out", rows)
+    jk = jk_in is not None or jk_out is not None
+    if jk:
+        if jk_in is None or jk_out is None or transpose_w:
+            raise RuntimeError("jk_in and jk_out go together (and not with transpose_w)")
+        _check_rows(jk_in, "jk_in", rows)
+        _check_rows(jk_out, "jk_out", rows)
+    chained = kidsum_in is not None or kidsum_out is not None
+    if chained and graph.kidsum_rows == 0 and not jk:
+        raise RuntimeError("this graph handle has no child-sum side buffer (kidsum_rows == 0)")
+    _check_rows(kidsum_in, "kidsum_in", graph.kidsum_rows * batch, optional=True)
+    _check_rows(kidsum_out, "kidsum_out", graph.kidsum_rows * batch, optional=True)
+    common = (graph._h, batch, x, weight, scale, shift, residual, relu)
+    if jk:
+        call("eg_gcn_layer_fwd_jk", *common, out, kidsum_in, kidsum_out, jk_in, jk_out)
+    elif chained:
+        call("eg_gcn_layer_fwd_chain", *common, transpose_w, out, kidsum_in, kidsum_out)
+    else:
+        call("eg_gcn_layer_fwd", *common, transpose_w, out)
+    return out
+
+
+def gcn_layer_cls_fwd(graph: Graph, batch: int, x: torch.Tensor, weight: torch.Tensor, scale, shift, residual, relu: bool,
+                      packed: dict, sigmoid: bool = False, kidsum_in: Optional[torch.Tensor] = None,
+                      jk_in: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Last layer + node-type filter + 4 classifier heads in one kernel -> logits [batch * (num_nodes - num_conn), 4] (the
+    connection nodes at the head of every frame have no logits row).
+    jk_in: running JumpingKnowledge('max') maximum of the earlier embeddings: the heads then see max(jk_in, layer output)."""
+    rows = graph.num_nodes * batch
+    _check_layer_args(rows, x, weight, scale, shift, residual)
+    _check_rows(kidsum_in, "kidsum_in", graph.kidsum_rows * batch, optional=True)
+    _check_rows(jk_in, "jk_in", rows, optional=True)
+    out = torch.empty((graph.num_nodes - graph.num_conn) * batch, 4, dtype=torch.float32, device=x.device)
+    call("eg_gcn_layer_cls_fwd", graph._h, batch, x, weight, scale, shift, residual, relu, kidsum_in, jk_in,
+         *[packed[k] for k in _HEAD_KEYS], sigmoid, out)
+    return out
+
+
+def new_kidsum(graph: Graph, batch: int) -> Optional[torch.Tensor]:
+    """Zero-filled child-sum side buffer [batch * kidsum_rows, 128] for chained layers, or None when the
+    topology does not qualify (generic CSR handles, irregular frames)."""
+    rows = graph.kidsum_rows
+    if rows == 0:
+        return None
+    return torch.zeros(rows * batch, C, device=graph.device, dtype=torch.float32)
+
+
+def gcn_aggregate(graph: Graph, batch: int, x: torch.Tensor) -> torch.Tensor:
+    """A_hat x (symmetric-normalised adjacency with self loops)."""
+    _check_rows(x, "x", graph.num_nodes * batch)
+    out = torch.empty_like(x)
+    call("eg_gcn_aggregate", graph._h, batch, x, out)
+    return out
+
+
+def linear128_fwd(x: torch.Tensor, weight: torch.Tensor, scale=None, shift=None, residual=None, relu: bool = False,
+                  transpose_w: bool = False) -> torch.Tensor:
+    _check_rows(x, "x")
+    _check_vec(scale, "scale", C)
+    _check_vec(shift, "shift", C)
+    _check_rows(residual, "residual", x.shape[0], optional=True)
+    out = torch.empty_like(x)
+    call("eg_linear128_fwd", x, x.shape[0], weight.contiguous(), scale, shift, residual, relu, transpose_w, out)
+    return out
+
+
+def classifier_fwd(h: torch.Tensor, batch: int, n_per_frame: int, row_lo: int, n_valid: int, packed: dict,
+                   sigmoid: bool = False) -> torch.Tensor:
+    """node-type filter (contiguous row range per frame) + the 4 heads -> [batch*n_valid, 4]."""
+    _check_rows(h, "h", batch * n_per_frame)
+    out = torch.empty(batch * n_valid, 4, dtype=torch.float32, device=h.device)
+    call("eg_classifier_fwd", h, batch, n_per_frame, row_lo, n_valid, *[packed[k] for k in _HEAD_KEYS], sigmoid, out)
+    return out

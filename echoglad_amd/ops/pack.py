@@ -1,0 +1,252 @@
+"""Pooling and packing: the average-pool pyramid (pool.hip) and the node-feature packing of level maps, with or without the
+1 x 1 convolution in front (pack.hip)."""
+from __future__ import annotations
+
+import ctypes as ct
+from typing import Optional
+
+import torch
+
+from ._core import C, _check, _check_rows, _check_vec, call
+
+
+def _addresses(tensors):
+    """void*[n] of the tensors' addresses (None: a null pointer)."""
+    return (ct.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def _ints(values):
+    return (ct.c_int * len(values))(*values)
+
+
+def pyramid_supported(x: torch.Tensor, sides) -> bool:
+    """eg_avg_pool_pyramid_* cover square float32 CUDA planes up to 512 x 512 and strictly ascending sides <= the frame."""
+    sides = list(sides)
+    return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[2] == x.shape[3] and x.shape[2] <= 512 and
+            1 <= len(sides) <= 16 and all(1 <= a < b for a, b in zip(sides, sides[1:])) and sides[-1] <= x.shape[2] and sides[0] >= 1)
+
+
+def _pool_fwd(x: torch.Tensor, sides):
+    B, Cn, Fr, _ = x.shape
+    maps = [torch.empty(B, Cn, p, p, dtype=torch.float32, device=x.device) for p in sides]
+    call("eg_avg_pool_pyramid_fwd", x, B * Cn, Fr, _ints(sides), len(sides), _addresses(maps))
+    return maps
+
+
+def _pool_bwd(grads, frame_grad, sides, shape, device):
+    B, Cn, Fr, _ = shape
+    dx = torch.empty(shape, dtype=torch.float32, device=device)
+    call("eg_avg_pool_pyramid_bwd", _addresses(grads), frame_grad, B * Cn, Fr, _ints(sides), len(sides), dx)
+    return dx
+
+
+class _AvgPoolPyramidFn(torch.autograd.Function):
+    """[B, C, F, F] -> tuple of F.adaptive_avg_pool2d(x, p) for every side p, one launch each way."""
+
+    @staticmethod
+    def forward(ctx, x, *sides):
+        x = x.contiguous()
+        ctx.meta = (tuple(sides), tuple(x.shape), x.device)
+        return tuple(_pool_fwd(x, list(sides)))
+
+    @staticmethod
+    def backward(ctx, *grads):
+        sides, shape, device = ctx.meta
+        gs = [g.contiguous() if g is not None else None for g in grads]
+        return (_pool_bwd(gs, None, list(sides), shape, device),) + (None,) * len(sides)
+
+
+def avg_pool_pyramid(x: torch.Tensor, sides):
+    """[F.adaptive_avg_pool2d(x, (p, p)) for p in sides] (strictly ascending) in one launch; differentiable w.r.t. x."""
+    if not pyramid_supported(x, sides):
+        raise RuntimeError("avg_pool_pyramid: square float32 CUDA planes up to 512 x 512, strictly ascending sides <= the frame")
+    return list(_AvgPoolPyramidFn.apply(x, *[int(p) for p in sides]))
+
+
+def _alloc_nodes(batch: int, n_rows: int, row_offset: int, used: int, device) -> torch.Tensor:
+    """[batch * n_rows, 128] for a packing call: rows no level covers (connection / coordinate nodes) read as zero."""
+    alloc = torch.empty if (row_offset == 0 and used == n_rows) else torch.zeros
+    return alloc(batch * n_rows, C, dtype=torch.float32, device=device)
+
+
+def _rows_used(maps) -> int:
+    return sum(int(m.shape[2]) ** 2 for m in maps)
+
+
+class _PyramidPackFn(torch.autograd.Function):
+    """create_node_pixels of the base model (models.py:511-523) as ONE autograd node: pooled pyramid of the frame embedding +
+    the frame itself -> node-major rows.  Forward: eg_avg_pool_pyramid_fwd + eg_pack_levels; backward: eg_unpack_levels +
+    eg_avg_pool_pyramid_bwd (the frame's own rows are added there: no second [B,128,F,F] gradient for autograd to sum)."""
+
+    @staticmethod
+    def forward(ctx, x, batch, n_rows, row_offset, out, *sides):
+        x = x.contiguous()
+        sides = list(sides)
+        maps = _pool_fwd(x, sides) + [x]
+        used = _rows_used(maps)
+        if out is not None:
+            nodes = _pack_out(out, [], batch, n_rows, row_offset, used)
+        else:
+            nodes = _alloc_nodes(batch, n_rows, row_offset, used, x.device)
+        _pack_call("eg_pack_levels", maps, nodes, batch, n_rows, row_offset)
+        ctx.meta = (batch, n_rows, row_offset, sides, tuple(x.shape))
+        if out is not None:
+            ctx.mark_dirty(out)
+        return nodes
+
+    @staticmethod
+    def backward(ctx, d_nodes):
+        batch, n_rows, row_offset, sides, shape = ctx.meta
+        grads = [torch.empty(shape[0], shape[1], p, p, dtype=torch.float32, device=d_nodes.device) for p in sides]
+        g_frame = torch.empty(shape, dtype=torch.float32, device=d_nodes.device)
+        _pack_call("eg_unpack_levels", grads + [g_frame], d_nodes.contiguous(), batch, n_rows, row_offset)
+        return (_pool_bwd(grads, g_frame, sides, shape, d_nodes.device),) + (None,) * (4 + len(sides))
+
+
+def pyramid_pack(x: torch.Tensor, sides, batch: int, n_rows: int, row_offset: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Pooled pyramid (sides ascending) of x [batch,128,F,F] + x itself, packed node-major [batch * n_rows, 128] like
+    ``pack_levels([adaptive_avg_pool2d(x, p) ...] + [x])``.  Differentiable w.r.t. x (not with ``out=``: written in place)."""
+    if out is not None and torch.is_grad_enabled() and x.requires_grad:
+        raise RuntimeError("pyramid_pack into out= is not differentiable: call it under torch.no_grad() or without out=")
+    return _PyramidPackFn.apply(x, int(batch), int(n_rows), int(row_offset), out, *[int(p) for p in sides])
+
+
+# ---------------------------------------------------------------------------
+# node-feature packing (pack.hip)
+# ---------------------------------------------------------------------------
+def _square_sides(tensors, name: str, channels: Optional[int], batch: int):
+    """Sides of contiguous CUDA float32 [batch, channels (None: any), side, side] tensors, 1..16 of them."""
+    if not 1 <= len(tensors) <= 16:
+        raise RuntimeError(f"1..16 {name}s supported")
+    for t in tensors:
+        _check(t, name, (batch, channels, None, None))
+        if t.shape[2] != t.shape[3]:
+            raise RuntimeError(f"{name} must be square, got {tuple(t.shape)}")
+    return [int(t.shape[2]) for t in tensors]
+
+
+def _pack_call(fn_name, maps, nodes, batch, n_rows, row_offset):
+    side = _ints(_square_sides(maps, "level map", C, batch))
+    if fn_name == "eg_pack_levels":
+        call(fn_name, _addresses(maps), side, len(maps), batch, n_rows, row_offset, nodes)
+    else:
+        call(fn_name, nodes, _addresses(maps), side, len(maps), batch, n_rows, row_offset)
+
+
+class _PackLevelsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, batch, n_rows, row_offset, *maps):
+        maps = [m.contiguous() for m in maps]
+        nodes = _alloc_nodes(batch, n_rows, row_offset, _rows_used(maps), maps[0].device)
+        _pack_call("eg_pack_levels", maps, nodes, batch, n_rows, row_offset)
+        ctx.meta = (batch, n_rows, row_offset, [tuple(m.shape) for m in maps])
+        return nodes
+
+    @staticmethod
+    def backward(ctx, d_nodes):
+        batch, n_rows, row_offset, shapes = ctx.meta
+        grads = [torch.empty(s, dtype=torch.float32, device=d_nodes.device) for s in shapes]
+        _pack_call("eg_unpack_levels", grads, d_nodes.contiguous(), batch, n_rows, row_offset)
+        return (None, None, None, *grads)
+
+
+def _pack_out(out: torch.Tensor, inputs, batch: int, n_rows: int, row_offset: int, used: int) -> torch.Tensor:
+    """``out=`` of the packing calls: the caller's [batch * n_rows, 128] buffer is written in place (a static node-feature
+    buffer that a captured HIP graph reads: nn.HierarchicalPatchModel.enable_hip_graph).  No autograd through it."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in inputs):
+        raise RuntimeError("pack into out= is not differentiable: call it under torch.no_grad() or without out=")
+    _check_rows(out, "out", batch * n_rows)
+    if row_offset > 0 or used < n_rows:              # rows no level covers (connection / coordinate nodes) read as zero, as without out=
+        v = out.view(batch, n_rows, C)
+        if row_offset > 0:
+            v[:, :row_offset].zero_()
+        if row_offset + used < n_rows:
+            v[:, row_offset + used:].zero_()
+    return out
+
+
+def pack_levels(maps, batch: int, n_rows: int, row_offset: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """NCHW level maps [batch,128,p,p] (coarse to fine) -> node-major [batch * n_rows, 128]; level l lands at rows
+    row_offset + sum_{k<l} p_k^2 of every frame.  Differentiable w.r.t. the maps (not with ``out=``: written in place)."""
+    if out is not None:
+        maps = [m.contiguous() for m in maps]
+        _pack_out(out, maps, int(batch), int(n_rows), int(row_offset), _rows_used(maps))
+        _pack_call("eg_pack_levels", maps, out, int(batch), int(n_rows), int(row_offset))
+        return out
+    return _PackLevelsFn.apply(int(batch), int(n_rows), int(row_offset), *maps)
+
+
+def _conv_pack_call(feats, weights, biases, nodes, batch, n_rows, row_offset):
+    n = len(feats)
+    if len(weights) != n or len(biases) != n:
+        raise RuntimeError("1..16 levels, one weight and one bias (or None) per level")
+    sides = _square_sides(feats, "level features", None, batch)
+    chans = [int(f.shape[1]) for f in feats]
+    for cin, w, b in zip(chans, weights, biases):
+        _check(w, "level weight", numel=C * cin)           # [128, cin(, 1, 1)]
+        if w.shape[0] != C:
+            raise RuntimeError(f"level weight must be [{C}, {cin}(, 1, 1)], got {tuple(w.shape)}")
+        _check_vec(b, "level bias", C)
+    call("eg_conv1x1_relu_pack_levels", _addresses(feats), _addresses(weights), _addresses(biases), _ints(chans), _ints(sides), n, batch,
+         n_rows, row_offset, nodes)
+
+
+class _ConvReluPackFn(torch.autograd.Function):
+    """relu(conv1x1(features[l])) of every level, packed node-major, in one launch.  The backward unpacks the node gradient to
+    NCHW (eg_unpack_levels) and lets torch differentiate the recomputed relu(conv2d) of each level (the small levels carry the
+    wide channel counts; the frame-sized one has 4 input channels)."""
+
+    @staticmethod
+    def forward(ctx, batch, n_rows, row_offset, n_levels, *tensors):
+        feats = [t.contiguous() for t in tensors[:n_levels]]
+        weights = [t.contiguous() for t in tensors[n_levels:2 * n_levels]]
+        biases = list(tensors[2 * n_levels:3 * n_levels])
+        nodes = _alloc_nodes(batch, n_rows, row_offset, _rows_used(feats), feats[0].device)
+        _conv_pack_call(feats, weights, [b.contiguous() if b is not None else None for b in biases], nodes, batch, n_rows, row_offset)
+        ctx.meta = (batch, n_rows, row_offset, n_levels)
+        ctx.has_bias = [b is not None for b in biases]
+        ctx.save_for_backward(*feats, *weights, *[b for b in biases if b is not None])
+        return nodes
+
+    @staticmethod
+    def backward(ctx, d_nodes):
+        batch, n_rows, row_offset, n = ctx.meta
+        saved = ctx.saved_tensors
+        feats, weights = saved[:n], saved[n:2 * n]
+        bl = list(saved[2 * n:])
+        biases = [bl.pop(0) if hb else None for hb in ctx.has_bias]
+        g_maps = [torch.empty(batch, C, f.shape[2], f.shape[3], dtype=torch.float32, device=d_nodes.device) for f in feats]
+        _pack_call("eg_unpack_levels", g_maps, d_nodes.contiguous(), batch, n_rows, row_offset)
+        gf, gw, gb = [], [], []
+        for l in range(n):
+            need = (ctx.needs_input_grad[4 + l], ctx.needs_input_grad[4 + n + l], biases[l] is not None and ctx.needs_input_grad[4 + 2 * n + l])
+            if not any(need):
+                gf.append(None); gw.append(None); gb.append(None)
+                continue
+            with torch.enable_grad():
+                f = feats[l].detach().requires_grad_(need[0])
+                w = weights[l].detach().requires_grad_(need[1])
+                b = biases[l].detach().requires_grad_(need[2]) if biases[l] is not None else None
+                y = torch.relu(torch.nn.functional.conv2d(f, w.view(C, -1, 1, 1), b))
+                ins = [t for t, k in ((f, need[0]), (w, need[1]), (b, need[2])) if k]
+                outs = list(torch.autograd.grad(y, ins, g_maps[l]))
+            gf.append(outs.pop(0) if need[0] else None)
+            gw.append(outs.pop(0).view_as(weights[l]) if need[1] else None)
+            gb.append(outs.pop(0) if need[2] else None)
+        return (None, None, None, None, *gf, *gw, *gb)
+
+
+def conv1x1_relu_pack_levels(feats, weights, biases, batch: int, n_rows: int, row_offset: int = 0,
+                             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """relu(Conv2d(C_l, 128, 1)(feats[l])) for every level (coarse to fine), written node-major [batch * n_rows, 128] like
+    `pack_levels` (models.py:707-710 + :726-756 in one launch).  Differentiable w.r.t. features, weights and biases (not with
+    ``out=``: written in place)."""
+    n = len(feats)
+    if out is not None:
+        feats = [f.contiguous() for f in feats]
+        weights = [w.detach().contiguous() for w in weights]
+        biases = [b.detach().contiguous() if b is not None else None for b in biases]
+        _pack_out(out, list(feats), int(batch), int(n_rows), int(row_offset), _rows_used(feats))
+        _conv_pack_call(feats, weights, biases, out, int(batch), int(n_rows), int(row_offset))
+        return out
+    return _ConvReluPackFn.apply(int(batch), int(n_rows), int(row_offset), n, *feats, *weights, *biases)
