@@ -243,7 +243,7 @@ def test_eval_mode_with_gradients(coord):
 
 def test_resolver_never_serves_a_stale_graph():
     """A loader that frees and re-allocates edge_index every batch gets the same address back from the caching
-    allocator; a different graph of the same shape must not hit the old handle (nn.py:65)."""
+    allocator; a different graph of the same shape must not hit the old handle (nn/_resolve.py: GraphResolver.resolve)."""
     conv = egnn.GCNConv(128, 128)
     fill_state_dict(conv, seed=1)
     w, b = conv.lin.weight.detach().clone(), conv.bias.detach().clone()

@@ -950,7 +950,7 @@ def test_cfg4_train_full_batch_32_properties():
 
 def test_in_place_backward_leaves_retained_and_hooked_gradients_intact():
     """The training step folds every coordinate update into the node that consumes the layer output, whose backward patches
-    rows IN PLACE only on the gradient buffer it has allocated itself (nn._CoordLayerTrainFn).  No incoming gradient is ever
+    rows IN PLACE only on the gradient buffer it has allocated itself (nn._train._TrainFn).  No incoming gradient is ever
     written to: there is no ownership heuristic to get wrong.  With a layer_output_hook the model takes the explicit route
     (separate nodes, copies).  A middle layer's output with retain_grad() and with a hook that KEEPS the gradient object must
     give the oracle's dL/dh, and the two routes must agree on every parameter gradient."""
@@ -1093,7 +1093,7 @@ def test_batchnorm_backward_sums_handed_down_by_the_dx_launch(monkeypatch, frame
     1 and 2 of the step run WITHOUT a sums pass of their own (src/core/models.py:333-335 backwards).  Against EG_SUMS_DOWN=0 (every
     layer sums its own dy and z in fp64): the same forward bit for bit, every gradient to the rounding of an fp32 partial sum, and
     the step is bit-reproducible run to run (the partials do not depend on who wins a tile queue)."""
-    from echoglad_amd import nn as egnn, ops
+    from echoglad_amd import ops
     hip, _ = model_pair(frame, naux, 3, coord=coord, seed=47, use_connection_nodes=conn)
     for m in hip.modules():
         if isinstance(m, torch.nn.Dropout):
@@ -1122,7 +1122,9 @@ def test_batchnorm_backward_sums_handed_down_by_the_dx_launch(monkeypatch, frame
         ((got ** 2).mean() + (0 if gc is None else (gc ** 2).mean() * 1e-3)).backward()
         res[knob] = (got.detach().clone(), None if gc is None else gc.detach().clone(),
                      {k: q.grad.clone() for k, q in hip.named_parameters()}, list(calls))
-        assert not egnn._SUMS_DOWN, "every handed-down entry was consumed"
+        # (the carrier is the step's per-layer boxes: both slots of every box are empty again after backward())
+        assert all(box == [None, None] for box in hip._down_boxes or ()), "every handed-down entry was consumed"
+        assert (hip._down_boxes is not None) == (knob[0] == "1" and ops.lower_sums_supported(hip._resolver.resolve(ei.to(DEV), x.shape[0])[0].bwd))
     # backward order: layer 3, 2, 1.  (given sums?, hands sums down?)
     given3 = res["1"][3][0][0]                                   # (layer 3's sums come from the heads' backward where that route applies)
     g_ = hip._resolver.resolve(ei.to(DEV), x.shape[0])[0]
