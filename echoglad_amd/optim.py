@@ -50,7 +50,12 @@ class Adam(torch.optim.Optimizer):
                 loss = closure()
         lib, stream = None, None
         for gi, group in enumerate(self.param_groups):
-            ps = [p for p in group["params"] if p.grad is not None]
+            ps, grads = [], []
+            for p in group["params"]:
+                g = p.grad
+                if g is not None:
+                    ps.append(p)
+                    grads.append(g)
             if not ps:
                 continue
             if not ps[0].is_cuda:
@@ -58,16 +63,7 @@ class Adam(torch.optim.Optimizer):
             if lib is None:
                 lib = _lib.load()
                 stream = ct.c_void_p(torch.cuda.current_stream().cuda_stream)
-            # the prepared launches of this group (pointer tables, step-count arrays) are kept while nothing moved: the same parameters with
-            # the same addresses and gradients at the same addresses (the caching allocator hands a step's gradients the same blocks
-            # again) -- checks and 82 ctypes structs per step were 0.2 ms of a batch-1 step the host is the bound of
-            key = (tuple(map(id, ps)), tuple(p.data_ptr() for p in ps), tuple(p.grad.data_ptr() for p in ps))
-            cache = self.__dict__.setdefault("_prepared", {}).setdefault(gi, {})
-            hit = cache.get(key)
-            if hit is None:                             # (the allocator cycles through a few sets of blocks for a step's gradients)
-                if len(cache) >= 4:
-                    cache.clear()
-                hit = cache[key] = (key, self._prepare(ps))
+            launches = self._launches_of(gi, ps, grads)
             b1, b2 = group["betas"]
             lr = group["lr"]
             lr_dev = None
@@ -75,7 +71,7 @@ class Adam(torch.optim.Optimizer):
                 if not lr.is_cuda or lr.dtype != torch.float32 or lr.numel() != 1:
                     raise RuntimeError("echoglad_amd.optim.Adam: a tensor lr must be a CUDA float32 scalar")
                 lr_dev, lr = ct.c_void_p(lr.data_ptr()), 0.0
-            for part, table, counts, _keep in hit[1]:
+            for part, table, counts, _views, _moments in launches:
                 _lib.check(lib.eg_adam_step(table, len(part), ct.c_void_p(counts.data_ptr()), float(lr), lr_dev, float(b1), float(b2),
                                             float(group["eps"]), float(group["weight_decay"]), int(bool(group["maximize"])), stream),
                            "eg_adam_step")
@@ -89,40 +85,70 @@ class Adam(torch.optim.Optimizer):
         self.__dict__.pop("_prepared", None)            # (the moments and counts are new tensors)
         self.__dict__.pop("_count_arrays", None)
 
-    def _prepare(self, ps):
-        """[(parameters, eg_adam_tensor table, step counts, tensors kept alive)] -- one entry per launch of up to 96 parameters."""
+    def _launches_of(self, gi, ps, grads, on_device=True):
+        """The prepared launches of group ``gi`` for the parameters ``ps`` (those with a gradient, in order; ``grads``: their
+        gradients).  They are kept while nothing moved: the same parameters at the same addresses, contiguous gradients at the same
+        addresses (the caching allocator hands a step's gradients the same blocks again) AND ``self.state`` still holding the very
+        count views and moment tensors the tables point at (``_prepared_valid``) -- checks and 82 ctypes structs per step were 0.2 ms
+        of a batch-1 step the host is the bound of.  ``on_device`` False: CPU tensors pass (the host-logic tests walk the cache
+        without a GPU; nothing is launched)."""
+        key = (tuple(map(id, ps)), tuple([p.data_ptr() for p in ps]), tuple([g.data_ptr() for g in grads]))
+        cache = self.__dict__.setdefault("_prepared", {}).setdefault(gi, {})
+        hit = cache.get(key)
+        if hit is not None and not (_prepared_valid(self.state, hit) and all([g.is_contiguous() for g in grads])):
+            del cache[key]
+            hit = None
+        if hit is None:                                 # (the allocator cycles through a few sets of blocks for a step's gradients)
+            if len(cache) >= 4:
+                cache.clear()
+            copied = not all(g.is_contiguous() for g in grads)
+            hit = self._prepare(ps, on_device)
+            if not copied:                              # (a gradient copied to a contiguous one is not at the key's address: not kept)
+                cache[key] = hit
+        return hit
+
+    def _prepare(self, ps, on_device=True):
+        """[(parameters, eg_adam_tensor table, step counts, their 0-d views, (exp_avg, exp_avg_sq) per parameter)] -- one entry per
+        launch of up to 96 parameters.  The views and moments are what ``state[p]`` holds at this moment: they keep the memory behind
+        the table alive and are what ``_prepared_valid`` compares ``state`` with.  An empty parameter is in no launch (eg_adam_step takes
+        no empty entry): it is left alone, as torch.optim.Adam leaves it."""
+        ps = [p for p in ps if p.numel() > 0]
         for p in ps:
-            if not p.is_cuda or p.dtype != torch.float32 or p.grad.is_sparse or p.grad.dtype != torch.float32:
+            if (on_device and not p.is_cuda) or p.dtype != torch.float32 or p.grad.is_sparse or p.grad.dtype != torch.float32:
                 raise RuntimeError("echoglad_amd.optim.Adam: CUDA float32 parameters with dense float32 gradients only")
             if not p.is_contiguous():
                 raise RuntimeError("echoglad_amd.optim.Adam: parameters must be contiguous")
             if not p.grad.is_contiguous():
-                p.grad = p.grad.contiguous()            # (its address is not the key's: prepared again next step -- correct, just not cached)
+                p.grad = p.grad.contiguous()
             st = self.state[p]
-            if "exp_avg" not in st:
-                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            for name in ("exp_avg", "exp_avg_sq"):
+                t = st.get(name)
+                if t is None:
+                    st[name] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                elif t.dtype != torch.float32 or t.device != p.device or t.numel() != p.numel() or not t.is_contiguous():
+                    raise RuntimeError(f"echoglad_amd.optim.Adam: state[p]['{name}'] must be a contiguous float32 tensor of the parameter's size on its device")
         out = []
         for lo in range(0, len(ps), _MAX_TENSORS):
             part = ps[lo:lo + _MAX_TENSORS]
-            counts = self._counts_of(part)
+            counts, views = self._counts_of(part)
             table = (_AdamTensor * len(part))()
-            keep = []
+            moments = []
             for k, p in enumerate(part):
                 st = self.state[p]
                 table[k] = _AdamTensor(p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel())
-                keep += [st["exp_avg"], st["exp_avg_sq"]]
-            out.append((part, table, counts, keep))
+                moments.append((st["exp_avg"], st["exp_avg_sq"]))
+            out.append((part, table, counts, views, moments))
         return out
 
     def _counts_of(self, part):
-        """The step counts of the parameters of one launch as ONE device array (the kernel takes steps[k]); ``state[p]["step"]`` are 0-d
-        views of it.  Kept while the same parameters come in the same order; otherwise (first step, a parameter that had no gradient
-        last time, a loaded state) re-assembled from the per-parameter counts -- torch's state layout stays the truth."""
+        """(array, views): the step counts of the parameters of one launch as ONE device array (the kernel takes steps[k]);
+        ``state[p]["step"]`` are 0-d views of it.  Kept while the same parameters come in the same order; otherwise (first step, a
+        parameter that had no gradient last time, a loaded state) re-assembled from the per-parameter counts -- torch's state layout
+        stays the truth."""
         key = tuple(id(p) for p in part)
         hit = self.__dict__.setdefault("_count_arrays", {}).get(key)
         if hit is not None and all(self.state[p].get("step") is v for p, v in zip(part, hit[1])):
-            return hit[0]
+            return hit
         dev = part[0].device
         vals = []
         for p in part:
@@ -136,4 +162,20 @@ class Adam(torch.optim.Optimizer):
         if len(self._count_arrays) > 8:
             self._count_arrays.clear()
         self._count_arrays[key] = (counts, views)
-        return counts
+        return counts, views
+
+
+def _prepared_valid(state, launches) -> bool:
+    """Whether prepared launches (``Adam._prepare``) still describe ``state``: for every parameter ``state[p]["step"]`` is the cached
+    view of the launch's count array and ``exp_avg`` / ``exp_avg_sq`` are the tensors whose addresses sit in the table.  Anything else
+    -- a step in between that left a parameter out (its neighbours' counts moved to another array), a moment or a count replaced,
+    ``state[p]`` cleared or deleted -- and the launch would advance counts and moments nobody looks at any more.  Identity checks on
+    plain objects only: this runs in every step.  (In-place edits -- ``zero_()``, ``copy_()``, ``fill_()`` -- write the memory the
+    table points at and need no new table.)"""
+    get = state.get
+    for part, _table, _counts, views, moments in launches:
+        for p, view, (m, v) in zip(part, views, moments):
+            st = get(p)
+            if st is None or st.get("step") is not view or st.get("exp_avg") is not m or st.get("exp_avg_sq") is not v:
+                return False
+    return True

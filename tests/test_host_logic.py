@@ -1,5 +1,6 @@
 """CPU: host-side logic that needs no GPU -- the stacked layout the heads' parameters live in and the packed gradients come back
-in, the hand-down of the BatchNorm-backward sums through the per-layer boxes, the optimizer's argument checks."""
+in, the hand-down of the BatchNorm-backward sums through the per-layer boxes, the optimizer's argument checks and what keeps or
+drops its prepared launches."""
 import pytest
 import torch
 
@@ -101,3 +102,146 @@ def test_adam_argument_checks_and_no_cpu_path():
     p.grad = torch.ones(3)
     with pytest.raises(RuntimeError):
         opt.step()                                                               # a CPU parameter: refused before any launch
+
+
+# ---- optim.Adam's prepared launches: what keeps one, what drops one (optim._prepared_valid), walked on CPU tensors --------------
+def _adam_on_cpu(n):
+    from echoglad_amd.optim import Adam
+    ps = [torch.nn.Parameter(torch.full((3,), float(k))) for k in range(n)]
+    for p in ps:
+        p.grad = torch.ones(3)                          # allocated once: the addresses never change, as gradients written in place
+    return Adam(ps, lr=1e-3), ps
+
+
+def _host_step(opt, ps):
+    """Adam.step without the launch: look the prepared launches up as step() does, then do to the counts what the kernel does."""
+    with_grad = [p for p in ps if p.grad is not None]
+    launches = opt._launches_of(0, with_grad, [p.grad for p in with_grad], on_device=False)
+    for _part, _table, counts, _views, _moments in launches:
+        counts += 1.0
+    return launches
+
+
+@pytest.mark.parametrize("n,skipped", [(3, 1), (106, 5)])
+def test_adam_prepared_launch_is_dropped_when_a_step_in_between_moved_the_counts(n, skipped):
+    """Step A: every parameter.  Step B: one without a gradient -- the others' counts move to another array.  Step C: every parameter
+    again, same addresses, so the key is A's: A's launch would count from A's array (t = 2 for tensors that are at t = 3).  (106
+    tensors: the skipped one is in the first launch of 96, so B's split is shifted against A's.)"""
+    from echoglad_amd.optim import _prepared_valid
+    opt, ps = _adam_on_cpu(n)
+    a = _host_step(opt, ps)
+    assert _prepared_valid(opt.state, a) and _host_step(opt, ps) is a            # nothing moved: kept, and used again
+    for p in ps:
+        assert float(opt.state[p]["step"]) == 2.0
+    parked, ps[skipped].grad = ps[skipped].grad, None
+    b = _host_step(opt, ps)
+    assert b is not a and not _prepared_valid(opt.state, a) and _prepared_valid(opt.state, b)
+    ps[skipped].grad = parked
+    c = _host_step(opt, ps)
+    assert c is not a and _prepared_valid(opt.state, c)
+    assert [float(opt.state[p]["step"]) for p in ps] == [3.0 if k == skipped else 4.0 for k in range(n)]
+    assert _host_step(opt, ps) is c
+    assert [float(opt.state[p]["step"]) for p in ps] == [4.0 if k == skipped else 5.0 for k in range(n)]
+    for launch in c:                                                             # the table's counts ARE the state's
+        for p, view in zip(launch[0], launch[3]):
+            assert opt.state[p]["step"] is view and view.data_ptr() >= launch[2].data_ptr()
+
+
+def _edit_exp_avg(opt, p):
+    opt.state[p]["exp_avg"] = torch.full((3,), 0.5)
+
+
+def _edit_exp_avg_sq(opt, p):
+    opt.state[p]["exp_avg_sq"] = torch.zeros(3)
+
+
+def _edit_step(opt, p):
+    opt.state[p]["step"] = torch.tensor(7.0)
+
+
+def _edit_step_number(opt, p):
+    opt.state[p]["step"] = 7
+
+
+def _edit_clear(opt, p):
+    opt.state[p].clear()
+
+
+def _edit_delete(opt, p):
+    del opt.state[p]
+
+
+@pytest.mark.parametrize("edit,step_after", [(_edit_exp_avg, 3.0), (_edit_exp_avg_sq, 3.0), (_edit_step, 8.0), (_edit_step_number, 8.0),
+                                             (_edit_clear, 1.0), (_edit_delete, 1.0)])
+def test_adam_prepared_launch_is_dropped_when_the_state_was_edited(edit, step_after):
+    from echoglad_amd.optim import _prepared_valid
+    opt, ps = _adam_on_cpu(3)
+    a = _host_step(opt, ps)
+    assert _host_step(opt, ps) is a
+    edit(opt, ps[1])
+    installed = {k: v for k, v in opt.state.get(ps[1], {}).items() if torch.is_tensor(v) and k != "step"}
+    assert not _prepared_valid(opt.state, a)
+    b = _host_step(opt, ps)
+    assert b is not a and _prepared_valid(opt.state, b) and _host_step(opt, ps) is not None
+    st = opt.state[ps[1]]
+    for k, v in installed.items():                                               # the tensor the user put there is the one in the table
+        assert st[k] is v and v.data_ptr() in (b[0][4][1][0].data_ptr(), b[0][4][1][1].data_ptr())
+    assert float(st["step"]) == step_after + 1.0 and float(opt.state[ps[0]]["step"]) == 4.0
+    assert st["exp_avg"].shape == st["exp_avg_sq"].shape == (3,)
+
+
+def test_adam_prepared_launch_survives_what_does_not_move_the_state():
+    """In-place edits write the memory the table points at; hyper-parameters are arguments of the launch, not of the table."""
+    from echoglad_amd.optim import _prepared_valid
+    opt, ps = _adam_on_cpu(3)
+    a = _host_step(opt, ps)
+    opt.state[ps[0]]["exp_avg"].zero_()
+    opt.state[ps[1]]["exp_avg_sq"].fill_(2.0)
+    opt.state[ps[2]]["step"].fill_(11.0)
+    ps[0].grad.copy_(torch.full((3,), 4.0))
+    opt.param_groups[0]["lr"] = 0.5
+    opt.param_groups[0]["betas"] = (0.5, 0.5)
+    assert _prepared_valid(opt.state, a) and _host_step(opt, ps) is a
+    assert float(opt.state[ps[2]]["step"]) == 12.0
+    sd = opt.state_dict()
+    assert _prepared_valid(opt.state, a)                                         # (saving does not move anything)
+    opt.load_state_dict(sd)
+    assert _host_step(opt, ps) is not a                                          # (loading does: new tensors)
+
+
+def test_adam_gradient_that_had_to_be_copied_is_not_cached_under_its_old_address():
+    """A non-contiguous gradient is copied; the table points at the copy.  The same view assigned again -- the same address in the
+    key -- must not find that table (the copy is gone or stale), nor may a contiguous gradient's table serve a strided view of it."""
+    opt, _ = _adam_on_cpu(1)
+    p = torch.nn.Parameter(torch.zeros(4, 4))
+    opt.add_param_group({"params": [p]})
+    buf = torch.arange(16.0).reshape(4, 4)
+
+    def tables(g):
+        p.grad = g
+        launches = opt._launches_of(1, [p], [p.grad], on_device=False)
+        return launches, launches[0][1][0].grad
+    a, addr_a = tables(buf.t())
+    assert p.grad.is_contiguous() and addr_a == p.grad.data_ptr() != buf.data_ptr()
+    b, addr_b = tables(buf.t())
+    assert b is not a and addr_b == p.grad.data_ptr() != buf.data_ptr()
+    c, addr_c = tables(buf)                                                      # contiguous at buf's address: kept ...
+    assert addr_c == buf.data_ptr() and tables(buf)[0] is c
+    d, addr_d = tables(buf.t())                                                  # ... but not for the transposed view at that address
+    assert d is not c and addr_d == p.grad.data_ptr() != buf.data_ptr() and torch.equal(p.grad, buf.t())
+
+
+def test_adam_leaves_an_empty_parameter_out_of_the_launch():
+    from echoglad_amd.optim import Adam
+    ps = [torch.nn.Parameter(torch.ones(3)), torch.nn.Parameter(torch.zeros(0)), torch.nn.Parameter(torch.ones(2, 0)), torch.nn.Parameter(torch.ones(1))]
+    for p in ps:
+        p.grad = torch.ones_like(p)
+    opt = Adam(ps)
+    launches = opt._launches_of(0, ps, [p.grad for p in ps], on_device=False)
+    assert len(launches) == 1 and [id(p) for p in launches[0][0]] == [id(ps[0]), id(ps[3])]
+    assert [launches[0][1][k].numel for k in range(2)] == [3, 1] and launches[0][2].shape == (2,)
+    assert opt._launches_of(0, ps, [p.grad for p in ps], on_device=False) is launches
+    only_empty = Adam([torch.nn.Parameter(torch.zeros(0))])
+    e = only_empty.param_groups[0]["params"][0]
+    e.grad = torch.zeros(0)
+    assert only_empty._launches_of(0, [e], [e.grad], on_device=False) == []

@@ -274,3 +274,107 @@ def test_cfg4_fixture_eval(golden_dir):
     assert np.abs(logits.numpy()[g["sample_rows"]] - g["logits_rows"]).max() < 5e-5
     assert abs(float(logits.double().sum()) - float(g["logits_sum"])) < 1e-6 * float(g["logits_abs_sum"])
     assert np.array_equal(O.landmark_argmax(logits, B, frame).numpy(), g["argmax"])
+
+
+# ---- oracle/adam_oracle.py: the fp64 form against torch's own Adam in double, and how hard the GPU tests' tolerance bites ----------
+def _adam_case(seed=11, n=1500, steps=6, t0=0):
+    """Parameters, per-step gradients (scaled differently per step, a few elements close to 0), and non-zero moments when the run
+    starts at a loaded step count t0 > 0."""
+    rs = np.random.RandomState(seed)
+    p = rs.standard_normal(n).astype(np.float32)
+    scales = [1.0, 0.3, 2.0, 0.7, 3.0, 1.5]
+    grads = [(rs.standard_normal(n) * scales[k % 6]).astype(np.float32) for k in range(steps)]
+    for g in grads:
+        g[::97] *= 1e-3
+    m = (rs.standard_normal(n) * 0.3).astype(np.float32) if t0 else np.zeros(n, np.float32)
+    v = (rs.standard_normal(n) ** 2 * 0.2).astype(np.float32) if t0 else np.zeros(n, np.float32)
+    return p, grads, m, v
+
+
+def _run_adam(step_fn, p, grads, m, v, t0, dtype, **hyper):
+    p, m, v = (a.astype(dtype) for a in (p, m, v))
+    for k, g in enumerate(grads):
+        p, m, v = step_fn(p, g, m, v, t0 + k + 1, dtype=dtype, **hyper)
+    return p, m, v
+
+
+@pytest.mark.parametrize("hyper", [dict(), dict(weight_decay=0.01), dict(maximize=True), dict(lr=3e-2, betas=(0.5, 0.9), eps=1e-3, weight_decay=0.1)])
+def test_adam_oracle_fp64_is_torch_adam_in_double(hyper):
+    """The oracle was written from the documented formulas; torch's single-tensor CPU implementation in float64 is an independent
+    evaluation of them.  One tensor sits a step out (its count stays behind)."""
+    from oracle import adam_oracle as AO
+    p0, grads, _, _ = _adam_case()
+    q0 = p0[:40] * 2
+    tp = [torch.nn.Parameter(torch.from_numpy(a.astype(np.float64))) for a in (p0, q0)]
+    opt = torch.optim.Adam(tp, foreach=False, **hyper)
+    o = AO.AdamOracle([p0, q0])
+    for k, g in enumerate(grads):
+        gs = [g, None if k == 2 else g[:40] * 0.5]
+        for t, gk in zip(tp, gs):
+            t.grad = None if gk is None else torch.from_numpy(gk.astype(np.float64))
+        opt.step()
+        o.step(gs, **hyper)
+    assert o.t == [6, 5] and [int(opt.state[t]["step"]) for t in tp] == [6, 5]
+    for k, t in enumerate(tp):
+        for got, want in ((o.p[k], t), (o.m[k], opt.state[t]["exp_avg"]), (o.v[k], opt.state[t]["exp_avg_sq"])):
+            want = want.detach().numpy()
+            assert np.abs(got - want).max() <= 1e-13 * max(1.0, np.abs(want).max())
+
+
+def _eps_inside_step(p, g, m, v, t, *, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, maximize=False, dtype=np.float32):
+    """adam_step with ONE mistake: eps added before the division by sqrt(1 - b2^t)."""
+    f = np.dtype(dtype).type
+    p, g, m, v = (np.asarray(a).astype(dtype) for a in (p, g, m, v))
+    b1, b2, lr, eps, wd = f(betas[0]), f(betas[1]), f(lr), f(eps), f(weight_decay)
+    g = -g if maximize else g
+    g = g + wd * p
+    m = b1 * m + (f(1) - b1) * g
+    v = b2 * v + (f(1) - b2) * g * g
+    step_size = f(np.float64(lr) / (1.0 - np.float64(b1) ** np.float64(t)))
+    bc2_sqrt = f(np.sqrt(1.0 - np.float64(b2) ** np.float64(t)))
+    return p - step_size * m / ((np.sqrt(v) + eps) / bc2_sqrt), m, v
+
+
+def _worst_ratio(got, want32, want64):
+    """max over p, exp_avg, exp_avg_sq of max|got - fp64 oracle| / bound: > 1 fails the GPU tests' comparison."""
+    from oracle import adam_oracle as AO
+    ratios = [np.abs(g.astype(np.float64) - w64).max() / AO.bound(w32, w64) for g, w32, w64 in zip(got, want32, want64)]
+    return max(ratios), ratios
+
+
+def test_adam_oracle_tolerance_bites():
+    """The bound of the GPU comparisons -- 4 * max(|fp32 oracle - fp64 oracle|, one fp32 ulp of the largest value) -- against what a
+    subtly wrong kernel would compute: each mistake, evaluated in fp32, is at least 100 bounds away; the fp32 oracle itself is inside."""
+    from oracle import adam_oracle as AO
+    f32 = AO.as_float32
+    for name, hyper, t0, wrong in [
+            ("step count behind by one", dict(lr=f32(1e-3)), 3, lambda h: _run_adam(AO.adam_step, *case, 2, np.float32, **h)),
+            ("eps inside the bias correction", dict(lr=f32(1e-3), eps=f32(1e-3)), 0, lambda h: _run_adam(_eps_inside_step, *case, 0, np.float32, **h)),
+            ("weight decay dropped", dict(lr=f32(1e-3), weight_decay=f32(0.01)), 0,
+             lambda h: _run_adam(AO.adam_step, *case, 0, np.float32, **dict(h, weight_decay=0.0)))]:
+        hyper = dict(hyper, betas=(f32(0.9), f32(0.999)))
+        case = _adam_case(t0=t0)
+        o64 = _run_adam(AO.adam_step, *case, t0, np.float64, **hyper)
+        o32 = _run_adam(AO.adam_step, *case, t0, np.float32, **hyper)
+        inside, _ = _worst_ratio(o32, o32, o64)
+        worst, ratios = _worst_ratio(wrong(hyper), o32, o64)
+        print(f"{name}: p, exp_avg, exp_avg_sq are {ratios[0]:.0f}, {ratios[1]:.0f}, {ratios[2]:.0f} bounds away; the fp32 oracle {inside:.2f}")
+        assert inside <= 0.25 + 1e-12, name               # (e32 / (4 max(e32, ulp)) by construction)
+        assert ratios[0] >= 100.0, (name, ratios)        # every one of them shows in the parameters
+        assert worst >= 100.0, (name, ratios)
+
+
+def test_adam_hyper_parameters_as_c_floats():
+    """eg_adam_step takes the hyper-parameters as C floats.  1 - float32(0.999) is 1.3e-5 (relative) off 1 - 0.999, and exp_avg_sq with
+    it; the bias correction uses the same rounded beta, so the parameters are a few fp32 ulps off the update with the exact
+    hyper-parameters, no more.  The GPU tests hand the fp64 oracle the rounded values: this is the size of what that leaves out."""
+    from oracle import adam_oracle as AO
+    case = _adam_case()
+    exact = dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8)
+    rounded = dict(lr=AO.as_float32(1e-3), betas=(AO.as_float32(0.9), AO.as_float32(0.999)), eps=AO.as_float32(1e-8))
+    pe, me, ve = _run_adam(AO.adam_step, *case, 0, np.float64, **exact)
+    pr, mr, vr = _run_adam(AO.adam_step, *case, 0, np.float64, **rounded)
+    rel_v = np.abs(vr / ve - 1).max()
+    assert 1.2e-5 < rel_v < 1.4e-5
+    assert np.abs(mr - me).max() < 5e-7 * np.abs(me).max()
+    assert np.abs(pr - pe).max() <= 4 * AO.ulp32(np.abs(pe).max())
