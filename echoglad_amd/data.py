@@ -51,6 +51,40 @@ def node_labels(coordinate: Sequence[int], frame_size: int, num_aux_graphs: int,
     return np.concatenate(parts)
 
 
+def _level_table(frame_size: int, num_aux_graphs: int, use_main_graph_only: bool = False):
+    from .losses import level_grids                 # (losses imports ops: only where a label table is asked for)
+    return level_grids(frame_size, num_aux_graphs, use_main_graph_only)
+
+
+def _check_label_coords(coords: np.ndarray, frame_size: int) -> None:
+    """IndexError where ``node_labels`` raises one: a coordinate outside [-F, F) (the main grid's ``y[i] = 1`` of any landmark)."""
+    bad = (coords < -frame_size) | (coords >= frame_size)
+    if bad.any():
+        v = int(coords[bad].ravel()[0])
+        raise IndexError(f"label index {v} is out of bounds for a grid of side {frame_size}")
+
+
+def label_rows(coords, frame_size: int, num_aux_graphs: int, use_main_graph_only: bool = False) -> np.ndarray:
+    """(h, w) of the landmarks, [K, 2] integers -> int64 [n_levels, K]: the frame-local row of every landmark's ``1`` on every
+    level, i.e. ``np.nonzero(node_labels(c, ...))`` per landmark, in integers (what eg_node_labels computes on the device):
+        aux levels, side p:   bin(v) = v * p // F  for 0 <= v < F,   p - 1  for -F <= v < 0
+        the main grid (last): bin(v) = v           for 0 <= v < F,   v + F  for -F <= v < 0
+    p is a power of two, so linspace(0, F, p + 1) is exact in fp64 and ``digitize(v) - 1 == v * p // F``.  IndexError exactly where
+    ``node_labels`` raises one."""
+    c = np.asarray(coords).astype(np.int64).reshape(-1, 2)
+    F = int(frame_size)
+    _check_label_coords(c, F)
+    levels = _level_table(F, num_aux_graphs, use_main_graph_only)
+    out = np.empty((len(levels), c.shape[0]), dtype=np.int64)
+    for l, (start, p) in enumerate(levels):
+        if l == len(levels) - 1:
+            b = np.where(c < 0, c + F, c)
+        else:
+            b = np.where(c < 0, p - 1, (c * p) // F)
+        out[l] = start + b[:, 0] * p + b[:, 1]
+    return out
+
+
 def draw_coords(frame_size: int, orig_frame_size: int = 224, rng=np.random) -> np.ndarray:
     """datasets.py:1421-1438: three draws of 4 integers (LVIDd, IVS, LVPW) scaled by F/224, assembled in (h, w)
     order as [lvid_top, lvid_bot, lvpw, ivs], each minus one (so -1 occurs and wraps in the labels)."""
@@ -63,11 +97,19 @@ def draw_coords(frame_size: int, orig_frame_size: int = 224, rng=np.random) -> n
 
 class SyntheticEchoDataset(torch.utils.data.Dataset):
     """Counterpart of ``DummyDataset``: 100 samples of N(0,1) frames with random landmark labels on the static
-    hierarchical graph.  ``transform`` maps the [1, 224, 224] frame to [1, F, F] (default: bilinear resize)."""
+    hierarchical graph.  ``transform`` maps the [1, 224, 224] frame to [1, F, F] (default: bilinear resize).
+
+    ``labels="coords"``: a sample carries ``label_coords`` (int32 [4, 2], the landmarks' (h, w)) and ``label_valid`` (float32 [4])
+    instead of the dense ``y`` / ``valid_labels`` -- same random draws, same landmarks; ``device_labels_`` expands them on the
+    device."""
 
     def __init__(self, num_aux_graphs: int, frame_size: int = 128, transform=None, average_coords=None,
                  main_graph_type: str = "grid", aux_graph_type: str = "grid", use_coordinate_graph: bool = False,
-                 use_connection_nodes: bool = False, use_main_graph_only: bool = False, length: int = 100):
+                 use_connection_nodes: bool = False, use_main_graph_only: bool = False, length: int = 100,
+                 labels: str = "dense"):
+        if labels not in ("dense", "coords"):
+            raise ValueError(f"labels must be 'dense' or 'coords', got {labels!r}")
+        self.labels = labels
         self.spec = TopologySpec(frame_size, num_aux_graphs, use_main_graph_only, use_coordinate_graph,
                                  use_connection_nodes, main_graph_type, aux_graph_type)
         self.topology: HierTopology = get_topology(self.spec)
@@ -81,6 +123,7 @@ class SyntheticEchoDataset(torch.utils.data.Dataset):
         self.length = length
         self.edge_index = torch.from_numpy(self.topology.edge_index())            # shared by every sample
         self.node_type = torch.from_numpy(self.topology.node_type())              # float64 like the reference
+        self._label_levels = tuple(_level_table(frame_size, num_aux_graphs, use_main_graph_only)) if labels == "coords" else None
 
     def __len__(self):
         return self.length
@@ -90,9 +133,16 @@ class SyntheticEchoDataset(torch.utils.data.Dataset):
         coords = draw_coords(self.frame_size)
         g = types.SimpleNamespace()
         g.x = frame
-        g.y = torch.from_numpy(np.stack([node_labels(c, self.frame_size, self.num_aux_graphs, self.use_main_graph_only)
-                                         for c in coords], axis=1))             # [N_grid, 4]
-        g.valid_labels = torch.ones_like(g.y)
+        if self.labels == "coords":
+            _check_label_coords(coords, self.frame_size)
+            g.label_coords = torch.from_numpy(coords.astype(np.int32))            # [4, 2]
+            g.label_valid = torch.ones(4, dtype=torch.float32)
+            g.label_levels = self._label_levels
+            g.label_frame_size = self.frame_size
+        else:
+            g.y = torch.from_numpy(np.stack([node_labels(c, self.frame_size, self.num_aux_graphs, self.use_main_graph_only)
+                                             for c in coords], axis=1))         # [N_grid, 4]
+            g.valid_labels = torch.ones_like(g.y)
         g.edge_index = self.edge_index
         g.node_type = self.node_type
         g.num_nodes = self.topology.num_nodes
@@ -113,8 +163,15 @@ def collate(samples: Sequence, topology: Optional[HierTopology] = None):
     out = types.SimpleNamespace()
     out.num_graphs = B
     out.x = torch.cat([s.x for s in samples], dim=0)
-    out.y = torch.cat([s.y for s in samples], dim=0)
-    out.valid_labels = torch.cat([s.valid_labels for s in samples], dim=0)
+    if hasattr(samples[0], "label_coords"):
+        # coordinate labels: 32 + 16 bytes per frame; device_labels_() expands them into y / valid_labels on the device
+        out.label_coords = torch.stack([s.label_coords for s in samples])          # [B, 4, 2] int32
+        out.label_valid = torch.stack([s.label_valid for s in samples])            # [B, 4]
+        out.label_levels = tuple(samples[0].label_levels)
+        out.label_frame_size = int(samples[0].label_frame_size)
+    else:
+        out.y = torch.cat([s.y for s in samples], dim=0)
+        out.valid_labels = torch.cat([s.valid_labels for s in samples], dim=0)
     if topology is not None:
         # what depends on (topology, B) only is built once and handed out again AS THE SAME TENSORS: the model resolves an
         # edge_index it has seen before by identity (no digest pass), and to_device() below moves such a tensor once per device
@@ -192,7 +249,17 @@ def copy_batch_(dst, src):
     would synchronise a step whose point is ~1 ms of GPU work behind one launch).  When ``src`` carries the collate() constant
     that ``dst``'s tensor was moved from (or ``dst``'s tensor itself) there is nothing to do; any other tensor is compared with
     the static one ONCE per static batch and attribute (equal: later batches are taken on trust by shape; different: ValueError
-    -- a captured step takes batches of ONE topology)."""
+    -- a captured step takes batches of ONE topology).
+
+    A coordinate-label source (``label_coords`` / ``label_valid``, 48 bytes per frame) leaves ``dst.y`` / ``dst.valid_labels``
+    alone: ``device_labels_(dst)`` rewrites them on the device.  The device cannot raise for a coordinate outside the frame, so a
+    CPU ``label_coords`` is checked here with ``label_rows``' rule (IndexError) before anything is copied."""
+    lc = getattr(src, "label_coords", None)
+    if torch.is_tensor(lc) and lc.device.type == "cpu":
+        frame_size = getattr(src, "label_frame_size", None) or getattr(dst, "label_frame_size", None)
+        if frame_size is None:
+            raise ValueError("a batch with label_coords needs label_frame_size (collate() records it)")
+        _check_label_coords(lc.numpy(), int(frame_size))
     verified = dst.__dict__.setdefault("_graph_consts_verified", set())
     for k, v in vars(src).items():
         if not torch.is_tensor(v):
@@ -215,3 +282,30 @@ def copy_batch_(dst, src):
             continue
         d.copy_(v, non_blocking=True)
     return dst
+
+
+def device_labels_(batch):
+    """Expands ``batch.label_coords`` [B, 4, 2] / ``batch.label_valid`` [B, 4] (a batch of ``labels="coords"`` samples, on the
+    device) into the dense ``batch.y`` / ``batch.valid_labels`` [B * N_grid, 4] the criteria and evaluators read: one launch
+    (ops.node_labels), no host synchronisation, so it can be the first node of a captured step.  The two dense tensors are
+    allocated at the first (eager) call and rewritten in place afterwards; inside a stream capture they must exist already.
+    A landmark outside [-F, F) gets no ``1`` (the host path raises IndexError: ``copy_batch_`` checks a CPU source).  A batch
+    without ``label_coords`` is returned as it is."""
+    coords = getattr(batch, "label_coords", None)
+    if coords is None:
+        return batch
+    from . import ops
+    levels = batch.label_levels
+    B = int(coords.shape[0])
+    y, valid = getattr(batch, "y", None), getattr(batch, "valid_labels", None)
+    if y is None or valid is None:
+        if coords.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("device_labels_: batch.y / batch.valid_labels do not exist yet and a stream capture must not allocate: "
+                               "call device_labels_(batch) once eagerly (a warm-up step does) before capturing")
+        n_rows = levels[-1][0] + levels[-1][1] ** 2
+        if y is None:
+            y = batch.y = torch.empty(B * n_rows, 4, dtype=torch.float32, device=coords.device)
+        if valid is None:
+            valid = batch.valid_labels = torch.empty(B * n_rows, 4, dtype=torch.float32, device=coords.device)
+    ops.node_labels(coords, getattr(batch, "label_valid", None), B, levels, batch.label_frame_size, y, valid)
+    return batch

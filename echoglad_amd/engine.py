@@ -59,6 +59,14 @@ def total_loss(losses) -> torch.Tensor:
     return total if total is not None else sum(losses.values())
 
 
+def _device_labels(batch):
+    """A batch of coordinate labels (``label_coords``, data.collate of ``labels="coords"`` samples): its dense ``y`` / ``valid_labels``
+    are written on the device first -- one launch, a node of the graph when the step is being captured."""
+    if getattr(batch, "label_coords", None) is not None:
+        from .data import device_labels_
+        device_labels_(batch)
+
+
 def forward_batch(model: Dict[str, torch.nn.Module], batch, use_coordinate_graph: bool):
     """engine.py:239-255: frame embeddings, then the landmark model on the collated batch."""
     x = model["embedder"](batch.x)
@@ -72,6 +80,7 @@ def train_step(model: Dict[str, torch.nn.Module], batch, criterion: Dict[str, ob
     """engine.py:239-291 for one batch.  ``reducer`` (parallel.GradientAllReducer) averages the gradients over the
     data-parallel ranks between backward and the optimizer step; it replaces torch_geometric's DataParallel
     (engine.py:105-110).  Returns (loss, losses dict, logits, coordinate predictions)."""
+    _device_labels(batch)
     preds, coord_preds = forward_batch(model, batch, use_coordinate_graph)
     coord_y = batch.node_coord_y if use_coordinate_graph else None
     losses = compute_loss(criterion, preds, batch.y, coord_preds, coord_y, batch.valid_labels, batch_size)
@@ -95,7 +104,8 @@ class GraphedTrainStep:
     work); at batch 32 the GPU is the bound and a replay changes nothing.
 
     ``loss_fn()`` -> loss, or (loss, *tensors to keep): it must read its inputs from tensors that stay where they are (write a new
-    batch INTO them before calling the step) and must not synchronise with the host.  Dropout: the seeds a train-mode forward
+    batch INTO them before calling the step) and must not synchronise with the host; with coordinate labels it starts with
+    ``data.device_labels_(static)``, which becomes a node of the graph.  Dropout: the seeds a train-mode forward
     draws on the host are frozen into the graph's kernel arguments, so the graph's first node bumps the device's dropout EPOCH
     (include/echoglad_hip.h: the kernels hash with seed + epoch) -- every replay draws fresh masks, its forward and backward see
     the same ones.  BatchNorm running statistics, ``num_batches_tracked`` and the optimizer's step count live on the device and
@@ -191,7 +201,8 @@ class GraphedEvalStep:
     of ``GraphedTrainStep``; it covers coordinate-graph models, which the model-level ``enable_hip_graph`` replay does not.
 
     ``static_batch``: a collated batch on the device (``data.to_device``); write every new batch INTO it (``data.copy_batch_``) before
-    calling the step.  ``pix2mm_x / pix2mm_y`` must be device tensors.  The graph reads ``static_batch.node_coords`` into a private
+    calling the step; a static batch of coordinate labels (``label_coords``) has its dense labels rebuilt by the graph's first node
+    (``data.device_labels_``).  ``pix2mm_x / pix2mm_y`` must be device tensors.  The graph reads ``static_batch.node_coords`` into a private
     buffer first: the caller's tensor is never written.  ``step()`` -> (preds, coord_preds, losses), the graph's static outputs, valid
     until the next call.  ``loss_avg()`` is the reference's ``loss_meter.avg`` (meters.AverageEpochMeter: an fp64 sum of
     ``total_loss * batch_size`` over an fp64 count, kept on the device and read back only there); ``reset_meter()`` zeroes it.
@@ -250,6 +261,8 @@ class GraphedEvalStep:
                 tuple((k, id(v)) for k, v in fold.items()))
 
     def _step(self):
+        # (coordinate labels: eval_step expands them into self._batch.y / .valid_labels first -- allocated by the eager warm-up,
+        # a node of the graph afterwards; self._batch shares label_coords with the caller's static batch)
         if self._coords is not None:
             self._coords.copy_(self.static_batch.node_coords)
         preds, coord_preds, losses = eval_step(self.model, self._batch, self.criterion, self.batch_size, self.use_coordinate_graph,
@@ -320,6 +333,7 @@ class GraphedEvalStep:
 def eval_step(model: Dict[str, torch.nn.Module], batch, criterion: Optional[Dict[str, object]], batch_size: int,
               use_coordinate_graph: bool = False, evaluators=None):
     """engine.py:340-460 for one batch (models in eval mode are the caller's business, like in the reference)."""
+    _device_labels(batch)
     preds, coord_preds = forward_batch(model, batch, use_coordinate_graph)
     coord_y = batch.node_coord_y if use_coordinate_graph else None
     losses = {}

@@ -86,8 +86,8 @@ extern "C" {
  * 135: eg_gcn_layer_bwd_lower, eg_bilinear4_bwd_rows_sums, eg_avg_pool_pyramid_fwd / _bwd, eg_criteria_* (round 6).
  * 136: eg_classifier_train_fwd_act(h_sparse), eg_classifier_bwd_sums(layer_residual, recompute_h).  137, 138: eg_coord_update_fwd / _bwd.  139, 140: eg_adam_step.
  * 141: eg_confusion_counts.  142: eg_bce_probs_fwd / _bwd, eg_criteria_ex_fwd / _bwd.
- * 143: eg_landmark_record_workspace_bytes, eg_landmark_record_hm, eg_landmark_record_coord. */
-#define EG_ABI_VERSION 143
+ * 143: eg_landmark_record_workspace_bytes, eg_landmark_record_hm, eg_landmark_record_coord.  144: eg_node_labels. */
+#define EG_ABI_VERSION 144
 
 #define EG_CHANNELS 128 /* node_embedding_dim == node_hidden_dim (configs/default.yml:13-14) */
 
@@ -642,6 +642,25 @@ int eg_landmark_record_hm(const float* logits, const float* labels, const float*
                           float* detail, int64_t capacity, int64_t* counter, eg_stream_t stream);
 int eg_landmark_record_coord(const float* coord_pred, const float* coord_y, int batch, const float* pix2mm_x, const float* pix2mm_y,
                              float* history, float* detail, int64_t capacity, int64_t* counter, eg_stream_t stream);
+
+/* ---- dense node labels from landmark coordinates (reference: create_node_labels, src/core/datasets.py:1586-1612) ----------
+ * What the criteria and evaluators above read as `labels` / `valid`, built on the device from what a sample actually carries:
+ *   coords [batch, 4, 2] i32  (h, w) of the 4 landmarks of every frame      valid4 [batch, 4] f32, or NULL (= 1)
+ *   labels [batch * n_rows, 4] f32 (16-byte aligned)                         valid  [batch * n_rows, 4] f32, or NULL (not written)
+ * level_start / level_side: HOST arrays of n_levels (1 .. 16) ints as eg_heatmap_expect_fwd takes them; the LAST level is the main
+ * grid and its side must equal frame_size (F); every other level is an aux level, whatever its side.
+ *   labels[b * n_rows + level_start[l] + i * p + j, c] = 1 iff (i, j) == (bin(h), bin(w)) of landmark c of frame b, else 0 (p = level_side[l])
+ *     aux level:  bin(v) = (v * p) / F (integer division) for 0 <= v < F;   p - 1 for -F <= v < 0
+ *     last level: bin(v) = v                              for 0 <= v < F;   v + F for -F <= v < 0
+ *   which is np.digitize(v, np.linspace(0, F, p + 1)) - 1 and numpy's wrap-around of a negative index, as the reference computes them.
+ *   A landmark with h or w outside [-F, F) -- an IndexError in the reference -- has no 1 on any level; the other channels are not
+ *   affected.  Rows outside every level are 0.
+ *   valid[b * n_rows + r, c] = valid4[b, c] (1 when valid4 is NULL).
+ * ONE launch; every element is written exactly once (no fill pass, no atomics); no allocation, no synchronisation: capturable.
+ * EG_ERR_ARG, nothing launched: batch < 1, n_levels outside 1 .. 16, a level that does not fit in n_rows, a last level whose side
+ * is not frame_size, NULL coords or labels, misaligned labels / valid. */
+int eg_node_labels(const int* coords, const float* valid4, int batch, int64_t n_rows, const int* level_start, const int* level_side,
+                   int n_levels, int frame_size, float* labels, float* valid, eg_stream_t stream);
 
 /* ---- node-feature packing (the step right before the hot path) -------------------------------------------
  * Reference: the per-sample loops at the tail of create_node_pixels (src/core/models.py:498-537, :590-636,
