@@ -9,6 +9,8 @@
  *   - node-type filter + 4 classifier MLPs + cat  (src/core/models.py:485-490)
  *   - bilinear_interpolation                      (src/core/models.py:539-553)
  *   - create_graphs / from_networkx               (src/core/datasets.py:1441-1584, :1392)
+ *   - DownConv / UpConv of the UNet front-end, eval (src/core/models.py:841-876: Conv2d 3x3 + ReLU + BatchNorm2d,
+ *     nn.Upsample, torch.cat, nn.AdaptiveMaxPool2d)
  *
  * Conventions
  *   - every data pointer is a DEVICE pointer, 16-byte aligned, row-major
@@ -86,8 +88,9 @@ extern "C" {
  * 135: eg_gcn_layer_bwd_lower, eg_bilinear4_bwd_rows_sums, eg_avg_pool_pyramid_fwd / _bwd, eg_criteria_* (round 6).
  * 136: eg_classifier_train_fwd_act(h_sparse), eg_classifier_bwd_sums(layer_residual, recompute_h).  137, 138: eg_coord_update_fwd / _bwd.  139, 140: eg_adam_step.
  * 141: eg_confusion_counts.  142: eg_bce_probs_fwd / _bwd, eg_criteria_ex_fwd / _bwd.
- * 143: eg_landmark_record_workspace_bytes, eg_landmark_record_hm, eg_landmark_record_coord.  144: eg_node_labels. */
-#define EG_ABI_VERSION 144
+ * 143: eg_landmark_record_workspace_bytes, eg_landmark_record_hm, eg_landmark_record_coord.  144: eg_node_labels.
+ * 145: eg_conv3x3_relu_bn_fwd, eg_adaptive_max_pool_fwd. */
+#define EG_ABI_VERSION 145
 
 #define EG_CHANNELS 128 /* node_embedding_dim == node_hidden_dim (configs/default.yml:13-14) */
 
@@ -661,6 +664,30 @@ int eg_landmark_record_coord(const float* coord_pred, const float* coord_y, int 
  * is not frame_size, NULL coords or labels, misaligned labels / valid. */
 int eg_node_labels(const int* coords, const float* valid4, int batch, int64_t n_rows, const int* level_start, const int* level_side,
                    int n_levels, int frame_size, float* labels, float* valid, eg_stream_t stream);
+
+/* ---- UNet front-end, inference (reference: DownConv / UpConv, src/core/models.py:841-876, in eval mode) ---------------------
+ * fp32 NCHW, contiguous, square maps of side 1 .. 512 with 1 .. 512 channels; 4-byte alignment is enough.
+ * eg_conv3x3_relu_bn_fwd: Conv2d(kernel 3, padding 1, zero padding) -> ReLU -> BatchNorm2d with running statistics, ONE launch:
+ *     out[b, o] = (relu(bias[o] + conv3x3(input)[b, o]) - bn_mean[o]) / sqrt(bn_var[o] + bn_eps) * bn_weight[o] + bn_bias[o]
+ *   (the reference's order: the BatchNorm comes AFTER the ReLU and is not folded into the weights; bn_weight may be negative).
+ *   input = the channel concatenation of
+ *     x0 [batch, c0, side0, side0] resized to side by nn.Upsample(size=side)'s nearest rule, src = min(dst * side0 / side, side0 - 1)
+ *        in integers (side0 == side: x0 as it is), and
+ *     x1 [batch, c1, side, side], or NULL together with c1 == 0,
+ *   so `upsample -> conv1` and `cat([x, skip]) -> conv2` of UpConv need no intermediate tensor.  weight [c_out, c0 + c1, 3, 3] is
+ *   torch's own Conv2d layout, read in place; bias, bn_weight, bn_bias [c_out] may be NULL (0, 1, 0); bn_mean, bn_var [c_out].
+ *   out [batch, c_out, side, side] must not alias an input.  Sides above 16 run an LDS-tiled kernel, sides up to 16 one that splits
+ *   K = 9 (c0 + c1) over the waves of a workgroup and adds the partial sums in wave order.
+ * eg_adaptive_max_pool_fwd: nn.AdaptiveMaxPool2d(side_out) on x [planes, side_in, side_in] -> out [planes, side_out, side_out];
+ *   window i = [floor(i side_in / side_out), ceil((i + 1) side_in / side_out)) in both directions; a NaN in a window is its result.
+ * Both: enqueue on the caller's stream, no allocation, no synchronisation, no atomics, a fixed summation order (bit-identical from
+ * run to run), capturable.  EG_ERR_ARG, nothing launched: a NULL required pointer, batch / planes < 1, a channel count or side
+ * < 1, x1 without c1 or c1 without x1, side_out > side_in, bn_eps < 0, out aliasing an input.  EG_ERR_UNSUPPORTED, nothing
+ * launched: a channel count (c0 + c1 or c_out) or a side above 512, batch above 65535. */
+int eg_conv3x3_relu_bn_fwd(const float* x0, int c0, int side0, const float* x1, int c1, int batch, int side, const float* weight,
+                           const float* bias, const float* bn_weight, const float* bn_bias, const float* bn_mean,
+                           const float* bn_var, float bn_eps, int c_out, float* out, eg_stream_t stream);
+int eg_adaptive_max_pool_fwd(const float* x, int planes, int side_in, int side_out, float* out, eg_stream_t stream);
 
 /* ---- node-feature packing (the step right before the hot path) -------------------------------------------
  * Reference: the per-sample loops at the tail of create_node_pixels (src/core/models.py:498-537, :590-636,
