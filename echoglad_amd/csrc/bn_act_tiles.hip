@@ -116,7 +116,7 @@ __device__ inline void act_pair(const float* __restrict__ z, const float* __rest
         return;
     }
     // ---- ragged patches, coordinate nodes, the last rows of a frame (rare): row by row, two rows per wave instruction.
-    // (No parent takes its children from such a segment: graph.hip switches the side buffer off otherwise.)
+    // (No parent takes its children from such a segment: topo_tables.hip switches the side buffer off otherwise.)
     const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + 4 * pl.q);
     const f32x4 sh = *reinterpret_cast<const f32x4*>(shift + 4 * pl.q);
 #pragma unroll 1

@@ -213,7 +213,7 @@ struct eg_graph {
     eg::TileDesc* tiles_dev;  // device [n_tiles] 2-D patch table of one frame (kind == GRAPH_TOPO)
     eg::SegDesc* segs_dev;    // device [n_tiles * 8] per-segment descriptors
     float* pats_dev;          // device [n_pats * 128] weight patterns (most segments share a handful)
-    float* patsq_dev;         // device [n_pats * 64] the same patterns in quad layout (graph.hip)
+    float* patsq_dev;         // device [n_pats * 64] the same patterns in quad layout (topo_tables.hip)
     int n_pats;
     int kid_rows;             // rows per frame of the child-sum side buffer (= aux nodes), 0 when the topology does not qualify
     int hybrid;               // 1: a closed-form topology whose stencil only the producer/consumer kernel implements ('grid-diagonal'
@@ -267,6 +267,9 @@ struct eg_graph {
     mutable std::atomic<unsigned char> any_launch;
     hipEvent_t era_event;                         // recorded on only_stream at the moment a second stream shows up: behind it lie all
     mutable std::atomic<unsigned char> era_recorded;   // launches that carry no event of their own (slot_used == 2)
+
+    // releases every device pointer above, conn_retired and the events (graph.hip): the only place a member is freed
+    ~eg_graph();
 
     // the slice of the queue ring for one launch on `stream` (graph.hip); EG_OK / EG_ERR_UNSUPPORTED / EG_ERR_HIP
     int acquire_queue_slice(hipStream_t stream, int** slice, int* slot) const;

@@ -2,11 +2,10 @@
 #include <hipcub/hipcub.hpp>
 
 #include <cmath>
-#include <algorithm>
-#include <map>
+#include <memory>
 #include <vector>
 
-#include "common.h"
+#include "topo_tables.h"
 #include <cstring>
 
 namespace eg {
@@ -19,12 +18,6 @@ int set_error(int code, const std::string& msg) {
 }
 
 #define EG_NO_STREAM_YET ((void*)(intptr_t)-1)          // eg_graph::only_stream before the handle's first launch
-
-#ifdef EG_DEBUG_TOPO
-#define EG_DEBUG_TOPO_ON 1          // -DEG_DEBUG_TOPO: why a handle has no child-sum side buffer, on stderr
-#else
-#define EG_DEBUG_TOPO_ON 0
-#endif
 
 static int env_int(const char* name, int dflt) {
     const char* v = getenv(name);
@@ -154,93 +147,31 @@ void eg_graph::commit_queue_slice(int slot, hipStream_t stream) const {
 
 namespace eg {
 
-static int create_slot_events(eg_graph* g) {
+// queue ring of a fresh handle (still to be zeroed) and the events that guard it
+static hipError_t alloc_queue_ring(eg_graph* g) {
+    const hipError_t e = hipMalloc((void**)&g->walk_counters, QUEUE_RING_BYTES);
+    if (e != hipSuccess) return e;
     for (int i = 0; i < QUEUE_SLOTS; ++i)
-        if (hipEventCreateWithFlags(&g->slot_event[i], hipEventDisableTiming) != hipSuccess) return EG_ERR_HIP;
-    if (hipEventCreateWithFlags(&g->era_event, hipEventDisableTiming) != hipSuccess) return EG_ERR_HIP;
-    return EG_OK;
+        if (hipEventCreateWithFlags(&g->slot_event[i], hipEventDisableTiming) != hipSuccess) return hipErrorOutOfMemory;
+    if (hipEventCreateWithFlags(&g->era_event, hipEventDisableTiming) != hipSuccess) return hipErrorOutOfMemory;
+    return hipSuccess;
 }
 
-// Python floor division
-static inline int floordiv(int a, int b) {
-    int q = a / b;
-    if ((a % b != 0) && ((a < 0) != (b < 0))) --q;
-    return q;
+// A handle under construction: whatever it has acquired when an error return drops it goes with it (~eg_graph).
+static std::unique_ptr<eg_graph> new_handle(int kind, int64_t n_nodes) {
+    std::unique_ptr<eg_graph> g(new eg_graph{});
+    g->only_stream.store(EG_NO_STREAM_YET, std::memory_order_relaxed);
+    g->kind = kind;
+    g->knobs = read_knobs();
+    g->n_nodes = n_nodes;
+    return g;
 }
 
-// Python `range(len)[start:stop]` with step 1 -> [lo, hi)
-static inline void py_slice(int len, int start, int stop, int& lo, int& hi) {
-    lo = start < 0 ? (len + start < 0 ? 0 : len + start) : (start > len ? len : start);
-    hi = stop < 0 ? (len + stop < 0 ? 0 : len + stop) : (stop > len ? len : stop);
-    if (hi < lo) hi = lo;
-}
-
-static int build_topo(int frame, int naux, int main_only, int coord_nodes, int conn_nodes, int diag_main, int diag_aux, Topo& T) {
-    if (frame < 2 || frame > 4096) return set_error(EG_ERR_ARG, "frame must be in [2, 4096]");
-    if (!main_only && (naux < 1 || naux + 1 > MAX_LEVELS)) return set_error(EG_ERR_ARG, "naux out of range");
-    T = Topo{};
-    T.n_aux = main_only ? 0 : naux;
-    T.n_conn = (!main_only && conn_nodes) ? naux + 1 : 0;     // datasets.py:1450-1456: only inside `if not use_main_graph_only`
-    int nid = T.n_conn;
-    T.diag_main = diag_main ? 1 : 0;
-    T.diag_aux = (!main_only && diag_aux) ? 1 : 0;
-    for (int k = 1; k <= T.n_aux; ++k) {
-        T.base[k - 1] = nid;
-        T.side[k - 1] = 1 << k;
-        nid += (1 << k) * (1 << k);
-    }
-    T.n_levels = T.n_aux + 1;
-    T.base[T.n_levels - 1] = nid;
-    T.side[T.n_levels - 1] = frame;
-    nid += frame * frame;
-    T.coord_base = nid;
-    if (!main_only && coord_nodes) nid += 4;       // datasets.py:1508-1523: only inside `if not use_main_graph_only`
-    T.n_nodes = nid;
-    T.frame = frame;
-    T.magic = ((1ull << 40) / (unsigned long long)frame) + 1ull;
-    if ((long long)frame * frame >= (1ll << 24)) return set_error(EG_ERR_UNSUPPORTED, "frame too large");
-    T.crop0 = 0; T.ncrop = 0;
-    if (T.n_aux > 0) {                             // datasets.py:1565-1567, Python slice semantics
-        const int p = 1 << T.n_aux;
-        const int half = frame / 2;
-        const int c0 = floordiv(p - half, 2);
-        int lo, hi;
-        py_slice(p, c0, c0 + half, lo, hi);
-        T.crop0 = lo; T.ncrop = hi - lo;
-    }
-    // per-level descriptors for the run-based stencil
-    T.n_desc = T.n_levels + (T.coord_base < T.n_nodes ? 1 : 0);
-    for (int l = 0; l < T.n_levels; ++l) {
-        LevelDesc& d = T.desc[l];
-        d = LevelDesc{};
-        const bool is_main = (l == T.n_levels - 1);
-        d.base = T.base[l];
-        d.side = T.side[l];
-        d.end = is_main ? T.coord_base : T.base[l + 1];
-        d.kind = is_main ? 1 : 0;
-        d.lg = is_main ? 0 : l + 1;
-        if (is_main) {
-            if (T.n_aux > 0) { d.pbase = T.base[l - 1]; d.pside = T.side[l - 1]; d.poff = T.crop0; d.plim = 2 * T.ncrop; }
-        } else {
-            if (l > 0) { d.pbase = T.base[l - 1]; d.pside = T.side[l - 1]; d.poff = 0; d.plim = d.side; }
-            d.cbase = T.base[l + 1]; d.cside = T.side[l + 1];
-            if (l + 1 < T.n_levels - 1) { d.clo = 0; d.chi = d.side; }
-            else { d.clo = T.crop0; d.chi = T.crop0 + T.ncrop; }
-        }
-    }
-    if (T.n_desc > T.n_levels) {
-        LevelDesc& d = T.desc[T.n_levels];
-        d = LevelDesc{};
-        d.base = T.coord_base; d.end = T.n_nodes; d.side = 4; d.kind = 2;
-    }
-    if (T.n_conn > 0) {                            // the connection nodes' pseudo-level, 8 nodes per (pseudo) row
-        if (T.n_desc + 1 > MAX_LEVELS + 1) return set_error(EG_ERR_ARG, "too many levels");
-        LevelDesc& d = T.desc[T.n_desc];
-        d = LevelDesc{};
-        d.base = 0; d.end = T.n_conn; d.side = 8; d.kind = KIND_CONN;
-        T.n_desc += 1;
-    }
-    return EG_OK;
+// device copy of a host table; an empty table still gets `min_elems` elements
+template <class T>
+static hipError_t upload(T** dev, const std::vector<T>& v, size_t min_elems = 0) {
+    const hipError_t e = hipMalloc((void**)dev, sizeof(T) * (v.size() > min_elems ? v.size() : min_elems));
+    return (e != hipSuccess || v.empty()) ? e : hipMemcpy(*dev, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice);
 }
 
 // ---------------------------------------------------------------- CSR build
@@ -378,25 +309,137 @@ static int csr_tiles(eg_graph* g, int mode, hipStream_t stream) {
         }
     }
     t_rowptr[slots] = (int)o;
-    EG_HIP_TRY(hipMalloc((void**)&g->t_rows, sizeof(int) * slots));
-    EG_HIP_TRY(hipMalloc((void**)&g->t_rowptr, sizeof(int) * (slots + 1)));
-    EG_HIP_TRY(hipMalloc((void**)&g->t_code, sizeof(int) * t_code.size()));
-    EG_HIP_TRY(hipMalloc((void**)&g->t_tgt, sizeof(int) * t_tgt.size()));
-    EG_HIP_TRY(hipMalloc((void**)&g->t_w, sizeof(float) * t_w.size()));
-    EG_HIP_TRY(hipMalloc((void**)&g->t_dis, sizeof(float) * slots));
-    EG_HIP_TRY(hipMemcpy(g->t_rows, t_rows.data(), sizeof(int) * slots, hipMemcpyHostToDevice));
-    EG_HIP_TRY(hipMemcpy(g->t_rowptr, t_rowptr.data(), sizeof(int) * (slots + 1), hipMemcpyHostToDevice));
-    EG_HIP_TRY(hipMemcpy(g->t_code, t_code.data(), sizeof(int) * t_code.size(), hipMemcpyHostToDevice));
-    EG_HIP_TRY(hipMemcpy(g->t_tgt, t_tgt.data(), sizeof(int) * t_tgt.size(), hipMemcpyHostToDevice));
-    EG_HIP_TRY(hipMemcpy(g->t_w, t_w.data(), sizeof(float) * t_w.size(), hipMemcpyHostToDevice));
-    EG_HIP_TRY(hipMemcpy(g->t_dis, t_dis.data(), sizeof(float) * slots, hipMemcpyHostToDevice));
+    EG_HIP_TRY(upload(&g->t_rows, t_rows));
+    EG_HIP_TRY(upload(&g->t_rowptr, t_rowptr));
+    EG_HIP_TRY(upload(&g->t_code, t_code));
+    EG_HIP_TRY(upload(&g->t_tgt, t_tgt));
+    EG_HIP_TRY(upload(&g->t_w, t_w));
+    EG_HIP_TRY(upload(&g->t_dis, t_dis));
     g->n_ctiles = n_tiles;
     return EG_OK;
 }
 
-static int csr_build(const int64_t* ei, int64_t n_nodes, int64_t n_edges, hipStream_t stream, const eg_graph* base, eg_graph** out);
+// the temporaries of one CSR build, freed on every way out of csr_fill
+struct CsrScratch {
+    int *keys = nullptr, *vals = nullptr, *keys_out = nullptr, *counts = nullptr;
+    unsigned long long* sym = nullptr;
+    void* tmp = nullptr;
+    ~CsrScratch() {
+        for (void* p : {(void*)keys, (void*)vals, (void*)keys_out, (void*)counts, (void*)sym, tmp})
+            if (p) (void)hipFree(p);
+    }
+};
+
+// rowptr / colidx / dis / nnz / symmetric of a fresh CSR handle from the edge list (csr_build)
+static int csr_fill(eg_graph* g, const int64_t* ei, int n, int m, hipStream_t stream, const eg_graph* base) {
+    const int64_t n_nodes = n, n_edges = m;
+    CsrScratch s;
+    size_t tmp_bytes = 0, tmp2 = 0;
+    const size_t mm = (size_t)(m > 0 ? m : 1);
+    EG_HIP_TRY(hipMalloc((void**)&s.keys, sizeof(int) * mm));
+    EG_HIP_TRY(hipMalloc((void**)&s.vals, sizeof(int) * mm));
+    EG_HIP_TRY(hipMalloc((void**)&s.keys_out, sizeof(int) * mm));
+    EG_HIP_TRY(hipMalloc((void**)&s.counts, sizeof(int) * ((size_t)n + 1)));
+    EG_HIP_TRY(hipMalloc((void**)&g->colidx, sizeof(int) * mm));
+    EG_HIP_TRY(hipMalloc((void**)&g->rowptr, sizeof(int) * ((size_t)n + 1)));
+    EG_HIP_TRY(hipMalloc((void**)&g->dis, sizeof(float) * (size_t)n));
+    EG_HIP_TRY(alloc_queue_ring(g));
+    EG_HIP_TRY(hipMemsetAsync(g->walk_counters, 0, QUEUE_RING_BYTES, stream));
+    EG_HIP_TRY(hipMemsetAsync(s.counts, 0, sizeof(int) * ((size_t)n + 1), stream));
+    int end_bit = 1;                             // key bits of the stable LSD radix sort by target: neighbours keep their edge_index order
+    while ((1ll << end_bit) <= n_nodes && end_bit < 32) ++end_bit;
+    if (m > 0) {
+        hipLaunchKernelGGL(k_edge_keys, dim3((m + 255) / 256), dim3(256), 0, stream, ei, n_edges, n, base ? 1 : 0, s.keys, s.vals, s.counts);
+        EG_HIP_TRY(hipGetLastError());
+        EG_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, s.keys, s.keys_out, s.vals, g->colidx, m, 0, end_bit, stream));
+    }
+    EG_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, s.counts, g->rowptr, n + 1, stream));
+    if (tmp2 > tmp_bytes) tmp_bytes = tmp2;
+    EG_HIP_TRY(hipMalloc(&s.tmp, tmp_bytes ? tmp_bytes : 16));
+    if (m > 0) {
+        size_t tb = tmp_bytes;
+        EG_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(s.tmp, tb, s.keys, s.keys_out, s.vals, g->colidx, m, 0, end_bit, stream));
+    }
+    {
+        size_t tb = tmp_bytes;
+        EG_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(s.tmp, tb, s.counts, g->rowptr, n + 1, stream));
+    }
+    unsigned long long sym_host[2] = {0, 0};
+    if (base) {
+        EG_HIP_TRY(hipMemcpyAsync(g->dis, base->dis, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice, stream));
+    } else {
+        hipLaunchKernelGGL(k_dis_from_counts, dim3((n + 255) / 256), dim3(256), 0, stream, s.counts, n, g->dis);
+        EG_HIP_TRY(hipGetLastError());
+        EG_HIP_TRY(hipMalloc((void**)&s.sym, 2 * sizeof(unsigned long long)));
+        EG_HIP_TRY(hipMemsetAsync(s.sym, 0, 2 * sizeof(unsigned long long), stream));
+        if (m > 0) {
+            int blocks = (m + 255) / 256;
+            hipLaunchKernelGGL(k_edge_sym, dim3(blocks > 2048 ? 2048 : blocks), dim3(256), 0, stream, ei, n_edges, n_nodes, s.sym);
+            EG_HIP_TRY(hipGetLastError());
+        }
+        EG_HIP_TRY(hipMemcpyAsync(sym_host, s.sym, sizeof(sym_host), hipMemcpyDeviceToHost, stream));
+    }
+    int nnz = 0;
+    EG_HIP_TRY(hipMemcpyAsync(&nnz, g->rowptr + n, sizeof(int), hipMemcpyDeviceToHost, stream));
+    EG_HIP_TRY(hipStreamSynchronize(stream));
+    g->nnz = nnz;
+    g->symmetric = base ? base->symmetric : (sym_host[0] == sym_host[1]);
+    return EG_OK;
+}
+
+// base == NULL: rows = targets, (deg+1)^-1/2 from the in-degrees.  base != NULL: rows = sources (the transposed adjacency
+// of the same edge_index), normalisation copied from base.
+static int csr_build(const int64_t* ei, int64_t n_nodes, int64_t n_edges, hipStream_t stream, const eg_graph* base, eg_graph** out) {
+    if (!out) return set_error(EG_ERR_ARG, "out is NULL");
+    *out = nullptr;
+    if (n_nodes <= 0 || n_nodes >= (1ll << 31) - 1 || n_edges < 0 || n_edges >= (1ll << 31) - 1)
+        return set_error(EG_ERR_ARG, "n_nodes / n_edges out of int32 range");
+    if (n_edges > 0 && !ei) return set_error(EG_ERR_ARG, "edge_index is NULL");
+    std::unique_ptr<eg_graph> g = new_handle(GRAPH_CSR, n_nodes);
+    int rc = csr_fill(g.get(), ei, (int)n_nodes, (int)n_edges, stream, base);
+    if (rc == EG_OK && g->knobs.csr_tiles > 0) rc = csr_tiles(g.get(), g->knobs.csr_tiles, stream);
+    if (rc != EG_OK) return rc;
+    *out = g.release();
+    return EG_OK;
+}
+
+// allocate and copy what build_topo_tables made for the handle
+static hipError_t upload_topo(eg_graph* g, const TopoTables& tt) {
+    hipError_t e = upload(&g->dis, tt.dis);
+    if (e == hipSuccess) e = alloc_queue_ring(g);
+    if (e == hipSuccess) e = hipMemset(g->walk_counters, 0, QUEUE_RING_BYTES);
+    if (e == hipSuccess) e = hipMalloc((void**)&g->topo_dev, sizeof(Topo));
+    if (e == hipSuccess) e = hipMemcpy(g->topo_dev, &g->topo, sizeof(Topo), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = upload(&g->tiles_dev, tt.tiles);
+    if (e == hipSuccess) e = upload(&g->segs_dev, tt.segs);
+    if (e == hipSuccess) e = upload(&g->pats_dev, tt.pats);
+    if (e == hipSuccess) e = upload(&g->patsq_dev, tt.patsq);
+    if (g->n_conn > 0) {
+        const size_t per_frame = (size_t)(g->conn_chunks + 2 * g->n_conn) * C;
+        if (e == hipSuccess) e = upload(&g->conn_table, tt.conn_table, 4);
+        if (e == hipSuccess) e = hipMalloc((void**)&g->conn_scratch, sizeof(float) * per_frame * g->conn_cap * QUEUE_SLOTS);
+    }
+    if (g->hybrid) {
+        if (e == hipSuccess) e = upload(&g->rowptr, tt.h_rowptr);
+        if (e == hipSuccess) e = upload(&g->colidx, tt.h_colidx, 1);
+    }
+    return e;
+}
 
 }  // namespace eg
+
+// The one owner of a handle's device resources: every way out of a create call that does not hand the handle over, and
+// eg_graph_destroy, end here.
+eg_graph::~eg_graph() {
+    for (void* p : {(void*)dis, (void*)topo_dev, (void*)tiles_dev, (void*)segs_dev, (void*)pats_dev, (void*)patsq_dev, (void*)walk_counters,
+                    (void*)rowptr, (void*)colidx, (void*)conn_table, (void*)conn_scratch, (void*)t_rows, (void*)t_rowptr, (void*)t_code,
+                    (void*)t_tgt, (void*)t_w, (void*)t_dis})
+        if (p) (void)hipFree(p);
+    for (float* p : conn_retired) (void)hipFree(p);
+    for (hipEvent_t ev : slot_event)
+        if (ev) (void)hipEventDestroy(ev);
+    if (era_event) (void)hipEventDestroy(era_event);
+}
 
 // ---- eg_debug_layer_timing_*: events around layer-kernel launches while armed (bench.py's in-step kernel durations) ----
 namespace {
@@ -463,329 +506,28 @@ int eg_topo_create(int frame, int naux, int main_only, int coord_nodes, int conn
     Topo T;
     int rc = build_topo(frame, naux, main_only, coord_nodes, conn_nodes, diag_main, diag_aux, T);
     if (rc != EG_OK) return rc;
-    const bool any_diag = T.diag_main || T.diag_aux || T.n_conn > 0;      // (any topology whose stencil lives in the producer/consumer kernel only)
-    // connection node wired to every node of level l (datasets.py:1512-1515: node g - 1 <-> aux level g, g = 1 .. naux - 1), or -1
-    auto hub_of_level = [&](int l) { return (T.n_conn > 0 && l <= T.n_aux - 2) ? l : -1; };
-    // level / position of a grid node, and whether its level is 'grid-diagonal'
-    auto level_diag = [&](int l) { return l == T.n_levels - 1 ? T.diag_main != 0 : T.diag_aux != 0; };
-    auto diag_ids = [&](int n, int (&out)[4]) -> int {          // the up-to-4 diagonal neighbours of node n (datasets.py:1469-1475)
-        if (n >= T.coord_base || n < T.n_conn) return 0;
-        const int l = level_of(T, n);
-        if (!level_diag(l)) return 0;
-        const int side = T.side[l], idx = n - T.base[l], r = idx / side, c = idx - r * side;
-        int k = 0;
-        for (int dr = -1; dr <= 1; dr += 2)
-            for (int dc = -1; dc <= 1; dc += 2)
-                if (r + dr >= 0 && r + dr < side && c + dc >= 0 && c + dc < side) out[k++] = n + dr * side + dc;
-        return k;
-    };
-    // every neighbour of node n (no self loop), sorted: grid stencil + diagonals + the level's connection node; connection nodes:
-    // the other connection nodes + every node of their level
-    Nbrs nb;
-    auto full_row = [&](int n, std::vector<int>& row) {
-        row.clear();
-        if (n < T.n_conn) {
-            for (int h = 0; h < T.n_conn; ++h) if (h != n) row.push_back(h);
-            if (n <= T.n_aux - 2)
-                for (int j = T.base[n]; j < T.base[n + 1]; ++j) row.push_back(j);
-            return;
-        }
-        neighbours(T, n, nb);
-        for (int sl = 1; sl < nb.count; ++sl)
-            if (nb.valid[sl]) row.push_back(nb.id[sl]);
-        int dg[4];
-        const int nd = diag_ids(n, dg);
-        row.insert(row.end(), dg, dg + nd);
-        if (n < T.coord_base) {
-            const int hub = hub_of_level(level_of(T, n));
-            if (hub >= 0) row.push_back(hub);
-        }
-        std::sort(row.begin(), row.end());
-    };
-    std::vector<float> dis(T.n_nodes);
-    {
-        std::vector<int> row;
-        for (int n = 0; n < T.n_nodes; ++n) {
-            full_row(n, row);
-            dis[n] = (float)(1.0 / std::sqrt((double)(row.size() + 1)));
-        }
-    }
-    // 'grid-diagonal' handles also carry the CSR of one frame (sorted by target, then source): every path but the
-    // producer/consumer kernel's stencil reads it (common.h eg_graph::hybrid)
-    std::vector<int> h_rowptr, h_colidx;
-    if (any_diag) {
-        h_rowptr.assign((size_t)T.n_nodes + 1, 0);
-        std::vector<int> row;
-        for (int n = 0; n < T.n_nodes; ++n) {
-            full_row(n, row);
-            h_colidx.insert(h_colidx.end(), row.begin(), row.end());
-            h_rowptr[(size_t)n + 1] = (int)h_colidx.size();
-        }
-    }
-    // 2-D patch table.  Order = depth-first post-order over the pyramid of 8x8 patches: the patches under a
-    // coarse patch are emitted (recursively, 2x2 blocks) before it, so vertical neighbours, parents and
-    // children are worked on close in time by the workgroups of one XCD and meet in its L2.  Patches that
-    // the pyramid does not reach (outside the centre crop, or a main-only graph) follow in 2x2-block order.
-    std::vector<TileDesc> tiles;
-    {
-        std::vector<std::vector<char>> seen(T.n_levels);
-        std::vector<int> tside(T.n_levels);
-        for (int l = 0; l < T.n_levels; ++l) {
-            tside[l] = (T.desc[l].side + 7) / 8;
-            seen[l].assign((size_t)tside[l] * tside[l], 0);
-        }
-        auto push = [&](int l, int ty, int tx) {
-            const LevelDesc& d = T.desc[l];
-            const int r0 = ty * 8, c0 = tx * 8;
-            tiles.push_back(TileDesc{l, r0, c0, d.side - r0 < 8 ? d.side - r0 : 8, d.side - c0 < 8 ? d.side - c0 : 8, 0, 0, 0});
-        };
-        // explicit stack: (level, ty, tx, state)
-        struct Item { int l, ty, tx, expanded; };
-        auto visit = [&](int l0, int ty0, int tx0) {
-            std::vector<Item> st;
-            st.push_back(Item{l0, ty0, tx0, 0});
-            while (!st.empty()) {
-                Item it = st.back();
-                st.pop_back();
-                if (it.l < 0 || it.l >= T.n_levels || it.ty < 0 || it.tx < 0 || it.ty >= tside[it.l] || it.tx >= tside[it.l]) continue;
-                char& sn = seen[it.l][(size_t)it.ty * tside[it.l] + it.tx];
-                if (it.expanded) { push(it.l, it.ty, it.tx); continue; }
-                if (sn) continue;
-                sn = 1;
-                st.push_back(Item{it.l, it.ty, it.tx, 1});
-                const LevelDesc& d = T.desc[it.l];
-                if (d.kind != 0) continue;                        // main grid: leaf
-                // node range of the children of this patch, in the child level's coordinates
-                const int rlo = 2 * (it.ty * 8 - d.clo), rhi = 2 * (it.ty * 8 + 8 - d.clo);
-                const int clo = 2 * (it.tx * 8 - d.clo), chi = 2 * (it.tx * 8 + 8 - d.clo);
-                const int cl = it.l + 1;
-                const int climit = 2 * (d.chi - d.clo);
-                const int r_a = rlo < 0 ? 0 : rlo, r_b = rhi > climit ? climit : rhi;
-                const int c_a = clo < 0 ? 0 : clo, c_b = chi > climit ? climit : chi;
-                if (r_a >= r_b || c_a >= c_b) continue;
-                for (int ty = (r_b - 1) / 8; ty >= r_a / 8; --ty)        // reversed: the stack pops them in order
-                    for (int tx = (c_b - 1) / 8; tx >= c_a / 8; --tx) st.push_back(Item{cl, ty, tx, 0});
-            }
-        };
-        if (T.n_aux > 0) visit(0, 0, 0);
-        for (int l = 0; l < T.n_levels; ++l) {                    // whatever the pyramid did not reach: 2x2-block order
-            const int ts = tside[l];
-            for (int by = 0; by < ts; by += 2)
-                for (int bx = 0; bx < ts; bx += 2)
-                    for (int dy = 0; dy < 2; ++dy)
-                        for (int dx = 0; dx < 2; ++dx) {
-                            const int ty = by + dy, tx = bx + dx;
-                            if (ty < ts && tx < ts && !seen[l][(size_t)ty * ts + tx]) { seen[l][(size_t)ty * ts + tx] = 1; push(l, ty, tx); }
-                        }
-        }
-        if (T.coord_base < T.n_nodes) {
-            const LevelDesc& d = T.desc[T.n_levels];
-            tiles.push_back(TileDesc{T.n_levels, 0, 0, 1, d.end - d.base, 0, 0, 0});
-        }
-        for (int h0 = 0; h0 < T.n_conn; h0 += 8)           // connection nodes: 8 per pseudo-tile (one segment each)
-            tiles.push_back(TileDesc{T.n_desc - 1, h0 / 8, 0, 1, T.n_conn - h0 < 8 ? T.n_conn - h0 : 8, 0, 0, 0});
-    }
-    // Per-segment descriptors (8 per patch) and the table of distinct weight patterns.  A pattern is the 64 + 64
-    // lane weights of a segment: lane (u, s) -> valid(slot s of node u) ? (deg + 1)^-1/2 of that neighbour : 0.
-    // Interior segments of a level all share one pattern, so the table stays at a few dozen entries.
-    std::vector<SegDesc> segs(tiles.size() * 8);
-    std::vector<float> pats;
-    std::vector<float> pat_extra;                     // 5 floats per pattern (see `w` below)
-    int kid_rows = 0;
-    bool kidsum_ok = false;
-    {
-        kid_rows = (T.n_aux > 0 && T.n_levels > 1) ? T.base[T.n_levels - 1] : 0;
-        kidsum_ok = kid_rows > 0;
-        std::map<std::vector<float>, int> pat_index;
-        auto clampi = [](int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); };
-        const int n_frame = T.n_nodes, hi8 = n_frame - 8, last = n_frame - 1;
-        std::vector<float> w(128 + 5);                // lane weights + {diagonal?, edge weights of the row above (l, r) and below (l, r)}
-        for (size_t t = 0; t < tiles.size(); ++t) {
-            const TileDesc& td = tiles[t];
-            const LevelDesc& d = T.desc[td.level];
-            for (int tr = 0; tr < 8; ++tr) {
-                SegDesc sd{};
-                sd.n_first = d.base + (td.r0 + tr) * d.side + td.c0;
-                sd.cnt = tr < td.nrows ? td.ncols : 0;
-                const int idx = sd.n_first - d.base;
-                const bool grid = d.kind == KIND_AUX || d.kind == KIND_MAIN;       // (not the coordinate / connection pseudo-levels)
-                const int r = grid ? idx / d.side : 0;
-                const int c0 = idx - r * d.side;
-                const int cb = d.cbase + 2 * (r - d.clo) * d.cside + 2 * (c0 - d.clo);
-                const bool kids = d.kind == KIND_AUX && r >= d.clo && r < d.chi && c0 < d.chi && c0 + 8 > d.clo;   // some node of the segment has children
-                // per-node scalar path: coordinate K4, and segments so close to the end of the frame that a run of
-                // 8 rows (self / below / children) would have to be clamped while some of its rows are real neighbours
-                // (the rows below the LAST grid row are no neighbours: their clamped run carries weight 0)
-                const bool below = grid && r < d.side - 1;
-                const bool ldiag = grid && level_diag(td.level);
-                // (a 'grid-diagonal' segment takes the run path only when it is a whole 8-node run: seg_wide.h row_sum3)
-                const bool slow = !grid || sd.n_first + 8 > n_frame || (below && sd.n_first + d.side + 8 > n_frame) ||
-                                  (kids && (cb < 0 || cb + d.cside + 16 > n_frame)) || (ldiag && sd.cnt != 8);
-                sd.mode = sd.cnt == 0 ? 0 : (d.kind == KIND_CONN ? 3 : (slow ? 2 : 1));
-                sd.aux = (d.kind == KIND_AUX ? 1 : 0) | (ldiag ? 2 : 0) | (d.kind == KIND_AUX ? (hub_of_level(td.level) + 1) << 2 : 0);
-                if (sd.mode == 1) {
-                    sd.up0 = clampi(sd.n_first - d.side, 0, hi8);
-                    sd.down0 = clampi(sd.n_first + d.side, 0, hi8);
-                    sd.par0 = clampi(d.pbase + (d.poff + (r >> 1)) * d.pside + d.poff + (c0 >> 1), 0, hi8);
-                    sd.left = clampi(sd.n_first - 1, 0, last);
-                    sd.right = clampi(sd.n_first + 8, 0, last);
-                    sd.c0 = clampi(cb, 0, hi8);
-                    sd.c1 = clampi(cb + 8, 0, hi8);
-                    sd.c2 = clampi(cb + d.cside, 0, hi8);
-                    sd.c3 = clampi(cb + d.cside + 8, 0, hi8);
-                    for (int lane = 0; lane < 64; ++lane) {
-                        const int u = lane >> 3, sl = lane & 7;
-                        const int n = sd.n_first + (u < sd.cnt ? u : sd.cnt - 1);
-                        neighbours(T, n, nb);
-                        w[lane] = nb.valid[sl] ? dis[nb.id[sl]] : 0.0f;
-                        const int sb = 8 + (sl & 1);
-                        w[64 + lane] = ((sd.aux & 1) && nb.valid[sb]) ? dis[nb.id[sb]] : 0.0f;
-                    }
-                    for (int e = 0; e < 5; ++e) w[128 + e] = 0.0f;
-                    if (ldiag) {                                // the nodes left / right of the 8-node runs above and below
-                        auto dnode = [&](int rr, int cc) { return (rr >= 0 && rr < d.side && cc >= 0 && cc < d.side) ? dis[d.base + rr * d.side + cc] : 0.0f; };
-                        w[128] = 1.0f;
-                        w[129] = dnode(r - 1, c0 - 1); w[130] = dnode(r - 1, c0 + 8);
-                        w[131] = dnode(r + 1, c0 - 1); w[132] = dnode(r + 1, c0 + 8);
-                    }
-                    auto it = pat_index.find(w);
-                    if (it == pat_index.end()) {
-                        it = pat_index.emplace(w, (int)pat_index.size()).first;
-                        pats.insert(pats.end(), w.begin(), w.begin() + 128);
-                        pat_extra.insert(pat_extra.end(), w.begin() + 128, w.end());
-                    }
-                    sd.pat = it->second;
-                }
-                segs[t * 8 + tr] = sd;
-            }
-            for (int tr = 0; tr < 8; tr += 2) {       // pad0 of an even patch row: it and the next row form a pair (seg_wide.h)
-                SegDesc& sa = segs[t * 8 + tr];
-                const SegDesc& sb = segs[t * 8 + tr + 1];
-                sa.pad0 = sa.mode == 1 && sb.mode == 1 && sa.aux == sb.aux && sa.par0 == sb.par0 && sa.down0 == sb.n_first &&
-                          sb.up0 == sa.n_first && sa.cnt == sb.cnt;
-                // pad1 = number of parents whose four children are exactly columns 2j, 2j+1 of this pair of rows
-                // (child-sum side buffer, gcn_layer_ps.hip).  Anything irregular switches the side buffer off.
-                if (sa.cnt > 0 && (d.kind == KIND_AUX || d.kind == KIND_MAIN)) {
-                    const int idx = sa.n_first - d.base, r = idx / d.side, c0 = idx - r * d.side;
-                    int npar = 0;
-                    if (r < d.plim) {
-                        const int cend = c0 + sa.cnt < d.plim ? c0 + sa.cnt : d.plim;
-                        npar = cend > c0 ? (cend - c0) / 2 : 0;
-                        if (cend > c0 && ((cend - c0) & 1)) { kidsum_ok = false; if (EG_DEBUG_TOPO_ON) fprintf(stderr, "kidsum off: odd t=%zu tr=%d\n", t, tr); }
-                    }
-                    const int par_raw = d.pbase + (d.poff + (r >> 1)) * d.pside + d.poff + (c0 >> 1);
-                    // ('grid-diagonal' levels of fewer than 8 columns run node by node -- rows pulled through the CSR, children
-                    //  included -- and never read the side buffer: child sums that nobody writes for THEIR rows are not missed)
-                    const bool parent_slow = td.level > 0 && level_diag(td.level - 1) && T.side[td.level - 1] < 8 && d.kind == KIND_AUX;
-                    if (npar > 0 && !parent_slow && (!sa.pad0 || par_raw != sa.par0 || par_raw + npar > kid_rows)) { kidsum_ok = false; if (EG_DEBUG_TOPO_ON) fprintf(stderr, "kidsum off: parent t=%zu tr=%d level=%d pad0=%d par_raw=%d par0=%d npar=%d kid_rows=%d modes %d %d\n", t, tr, td.level, sa.pad0, par_raw, sa.par0, npar, kid_rows, sa.mode, sb.mode); }
-                    sa.pad1 = npar;
-                    const bool kids = d.kind == KIND_AUX && ((r >= d.clo && r < d.chi) || (r + 1 >= d.clo && r + 1 < d.chi)) && c0 < d.chi && c0 + 8 > d.clo;
-                    const bool self_slow = level_diag(td.level) && d.side < 8;
-                    // the pair path reads runs of 8 child-sum rows from each segment's first node: they must stay inside the
-                    // frame's slice of the side buffer (tiny pyramids only: a 2x2 or 4x4 level right at its end; an over-read
-                    // past the LAST frame's slice left the allocation and aborted a test run once)
-                    if (kids && !self_slow && (sa.n_first + 8 > kid_rows || sb.n_first + 8 > kid_rows)) { kidsum_ok = false; if (EG_DEBUG_TOPO_ON) fprintf(stderr, "kidsum off: 8-row run past the side buffer t=%zu tr=%d\n", t, tr); }
-                    if (kids && !sa.pad0 && !self_slow) { kidsum_ok = false; if (EG_DEBUG_TOPO_ON) fprintf(stderr, "kidsum off: kids unpaired t=%zu tr=%d level=%d\n", t, tr, td.level); }      // a segment that would read the side buffer is not on the pair path
-                }
-            }
-        }
-        if (pats.empty()) { pats.assign(128, 0.0f); pat_extra.assign(5, 0.0f); }
-        if (EG_DEBUG_TOPO_ON) fprintf(stderr, "topo: %zu tiles, %zu patterns, kidsum %d\n", tiles.size(), pats.size() / 128, (int)kidsum_ok);
-    }
-    eg_graph* g = new eg_graph{};
-    g->only_stream.store(EG_NO_STREAM_YET, std::memory_order_relaxed);
-    g->kind = GRAPH_TOPO;
-    g->knobs = read_knobs();
-    g->n_nodes = T.n_nodes;
-    g->n_pats = (int)(pats.size() / 128);
-    // The same patterns in "quad" layout for the producer/consumer kernel, which keeps them in LDS: [pattern][row parity
-    // h][slot 0..7][k 0..3] = weight of (node 2k + h, slot); slot 6 = 1.0 when the node has children.  The outer
-    // neighbours of a segment's first and last node travel apart from the inner ones (seg_wide.h, segw_rows): node 0's
-    // left weight and node 7's right weight sit in slot 7 (k = 0 of h = 0, k = 3 of h = 1) and are zero in slots 3 / 4.
-    std::vector<float> patsq((size_t)g->n_pats * 64, 0.0f);
-    for (int pi = 0; pi < g->n_pats; ++pi)
-        for (int h = 0; h < 2; ++h)
-            for (int sl = 0; sl < 7; ++sl)
-                for (int k = 0; k < 4; ++k) {
-                    const float w = pats[(size_t)pi * 128 + (2 * k + h) * 8 + sl];
-                    const bool outer = (sl == 3 && h == 0 && k == 0) || (sl == 4 && h == 1 && k == 3);
-                    patsq[(size_t)pi * 64 + h * 32 + sl * 4 + k] = outer ? 0.0f : (sl < 6 ? w : (w != 0.0f ? 1.0f : 0.0f));
-                    if (outer) patsq[(size_t)pi * 64 + h * 32 + 7 * 4 + k] = w;
-                }
-    for (int pi = 0; pi < g->n_pats && !pat_extra.empty(); ++pi) {
-        const float* ex = &pat_extra[(size_t)pi * 5];
-        if (ex[0] == 0.0f) continue;
-        // diagonal segment: slots 3 / 4 = edge nodes of the row above / below (seg_wide.h SLOT_EDGE_U / SLOT_EDGE_D), laid out like
-        // slot 7: the left edge belongs to node 0 (k = 0 of h = 0), the right edge to node 7 (k = 3 of h = 1)
-        for (int h = 0; h < 2; ++h)
-            for (int k = 0; k < 4; ++k) { patsq[(size_t)pi * 64 + h * 32 + 3 * 4 + k] = 0.0f; patsq[(size_t)pi * 64 + h * 32 + 4 * 4 + k] = 0.0f; }
-        patsq[(size_t)pi * 64 + 0 * 32 + 3 * 4 + 0] = ex[1]; patsq[(size_t)pi * 64 + 1 * 32 + 3 * 4 + 3] = ex[2];
-        patsq[(size_t)pi * 64 + 0 * 32 + 4 * 4 + 0] = ex[3]; patsq[(size_t)pi * 64 + 1 * 32 + 4 * 4 + 3] = ex[4];
-    }
-    // chained layers run the producer/consumer kernel, which keeps the pattern table in LDS beside its tile buffers
-    const size_t ps_lds = (size_t)(4 * TILE * LDA + 16 + 64 + 2 * TILE + (pats.size() / 128) * 64 + 4 * C) * sizeof(float);   // incl. the fused-classifier tables
-    g->kid_rows = (kidsum_ok && ps_lds <= 160 * 1024) ? kid_rows : 0;
-    g->flat = (T.n_levels == 1 && T.n_desc == 1 && ps_lds <= 160 * 1024) ? 1 : 0;
+    TopoTables tt;
+    rc = build_topo_tables(T, tt);
+    if (rc != EG_OK) return rc;
+    std::unique_ptr<eg_graph> g = new_handle(GRAPH_TOPO, T.n_nodes);
     g->topo = T;
-    g->n_tiles = (int)tiles.size();
-    hipError_t e = hipMalloc((void**)&g->dis, sizeof(float) * T.n_nodes);
-    if (e == hipSuccess) e = hipMemcpy(g->dis, dis.data(), sizeof(float) * T.n_nodes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void**)&g->walk_counters, QUEUE_RING_BYTES);
-    if (e == hipSuccess) e = hipMemset(g->walk_counters, 0, QUEUE_RING_BYTES);
-    if (e == hipSuccess && create_slot_events(g) != EG_OK) e = hipErrorOutOfMemory;
-    if (e == hipSuccess) e = hipMalloc((void**)&g->topo_dev, sizeof(Topo));
-    if (e == hipSuccess) e = hipMemcpy(g->topo_dev, &T, sizeof(Topo), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void**)&g->tiles_dev, sizeof(TileDesc) * tiles.size());
-    if (e == hipSuccess) e = hipMemcpy(g->tiles_dev, tiles.data(), sizeof(TileDesc) * tiles.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void**)&g->segs_dev, sizeof(SegDesc) * segs.size());
-    if (e == hipSuccess) e = hipMemcpy(g->segs_dev, segs.data(), sizeof(SegDesc) * segs.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void**)&g->pats_dev, sizeof(float) * pats.size());
-    if (e == hipSuccess) e = hipMemcpy(g->pats_dev, pats.data(), sizeof(float) * pats.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void**)&g->patsq_dev, sizeof(float) * patsq.size());
-    if (e == hipSuccess) e = hipMemcpy(g->patsq_dev, patsq.data(), sizeof(float) * patsq.size(), hipMemcpyHostToDevice);
+    g->n_tiles = (int)tt.tiles.size();
+    g->n_pats = tt.n_pats;
+    g->kid_rows = tt.kid_rows;
+    g->flat = tt.flat;
     if (T.n_conn > 0) {
-        // chunks of <= 256 rows over the levels that hang on a connection node (levels 0 .. naux - 2): the pre-pass (conn.hip) sums
-        // (deg + 1)^-1/2 x over a chunk per workgroup, then over a level's chunks in order
-        std::vector<int> table;
-        for (int l = 0; l <= T.n_aux - 2; ++l)
-            for (int r0 = T.base[l]; r0 < T.base[l + 1]; r0 += 256) {
-                const int rows = T.base[l + 1] - r0 < 256 ? T.base[l + 1] - r0 : 256;
-                table.insert(table.end(), {l, r0, rows, 0});
-            }
         g->n_conn = T.n_conn;
-        g->conn_chunks = (int)(table.size() / 4);
+        g->conn_chunks = tt.conn_chunks;
         g->conn_cap = 8;                                   // frames the scratch holds at first (it grows: conn.hip)
-        if (g->conn_cap < 1) g->conn_cap = 1;
-        const size_t per_frame = (size_t)(g->conn_chunks + 2 * T.n_conn) * C;
-        if (e == hipSuccess) e = hipMalloc((void**)&g->conn_table, sizeof(int) * (table.empty() ? 4 : table.size()));
-        if (e == hipSuccess && !table.empty()) e = hipMemcpy(g->conn_table, table.data(), sizeof(int) * table.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMalloc((void**)&g->conn_scratch, sizeof(float) * per_frame * g->conn_cap * QUEUE_SLOTS);
     }
-    if (any_diag) {
+    if (tt.hybrid) {
         g->hybrid = 1;
-        g->nnz = (int64_t)h_colidx.size();
+        g->nnz = (int64_t)tt.h_colidx.size();
         g->symmetric = 1;
-        if (e == hipSuccess) e = hipMalloc((void**)&g->rowptr, sizeof(int) * h_rowptr.size());
-        if (e == hipSuccess) e = hipMemcpy(g->rowptr, h_rowptr.data(), sizeof(int) * h_rowptr.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMalloc((void**)&g->colidx, sizeof(int) * (h_colidx.empty() ? 1 : h_colidx.size()));
-        if (e == hipSuccess && !h_colidx.empty()) e = hipMemcpy(g->colidx, h_colidx.data(), sizeof(int) * h_colidx.size(), hipMemcpyHostToDevice);
     }
-    if (e != hipSuccess) {
-        if (g->segs_dev) (void)hipFree(g->segs_dev);
-        if (g->pats_dev) (void)hipFree(g->pats_dev);
-        if (g->patsq_dev) (void)hipFree(g->patsq_dev);
-        if (g->dis) (void)hipFree(g->dis);
-        if (g->topo_dev) (void)hipFree(g->topo_dev);
-        if (g->tiles_dev) (void)hipFree(g->tiles_dev);
-        if (g->walk_counters) (void)hipFree(g->walk_counters);
-        if (g->rowptr) (void)hipFree(g->rowptr);
-        if (g->colidx) (void)hipFree(g->colidx);
-        if (g->conn_table) (void)hipFree(g->conn_table);
-        if (g->conn_scratch) (void)hipFree(g->conn_scratch);
-        delete g;
-        return set_error(EG_ERR_HIP, std::string("eg_topo_create: ") + hipGetErrorString(e));
-    }
-    *out = g;
+    const hipError_t e = upload_topo(g.get(), tt);
+    if (e != hipSuccess) return set_error(EG_ERR_HIP, std::string("eg_topo_create: ") + hipGetErrorString(e));
+    *out = g.release();
     return EG_OK;
 }
 
@@ -802,132 +544,9 @@ int eg_graph_is_symmetric(const eg_graph* g) { return g && (g->kind == GRAPH_TOP
 
 }  // extern "C"
 
-// base == NULL: rows = targets, (deg+1)^-1/2 from the in-degrees.  base != NULL: rows = sources (the transposed adjacency
-// of the same edge_index), normalisation copied from base.
-static int eg::csr_build(const int64_t* ei, int64_t n_nodes, int64_t n_edges, hipStream_t stream, const eg_graph* base, eg_graph** out) {
-    if (!out) return set_error(EG_ERR_ARG, "out is NULL");
-    *out = nullptr;
-    if (n_nodes <= 0 || n_nodes >= (1ll << 31) - 1 || n_edges < 0 || n_edges >= (1ll << 31) - 1)
-        return set_error(EG_ERR_ARG, "n_nodes / n_edges out of int32 range");
-    if (n_edges > 0 && !ei) return set_error(EG_ERR_ARG, "edge_index is NULL");
-    const int n = (int)n_nodes;
-    const int m = (int)n_edges;
-    eg_graph* g = new eg_graph{};
-    g->only_stream.store(EG_NO_STREAM_YET, std::memory_order_relaxed);
-    g->kind = GRAPH_CSR;
-    g->knobs = read_knobs();
-    g->n_nodes = n_nodes;
-    int *keys = nullptr, *vals = nullptr, *keys_out = nullptr, *counts = nullptr;
-    unsigned long long* sym = nullptr;
-    void* tmp = nullptr;
-    size_t tmp_bytes = 0, tmp2 = 0;
-    auto cleanup = [&](bool all) {
-        if (keys) (void)hipFree(keys);
-        if (vals) (void)hipFree(vals);
-        if (keys_out) (void)hipFree(keys_out);
-        if (counts) (void)hipFree(counts);
-        if (sym) (void)hipFree(sym);
-        if (tmp) (void)hipFree(tmp);
-        if (all) {
-            if (g->dis) (void)hipFree(g->dis);
-            if (g->rowptr) (void)hipFree(g->rowptr);
-            if (g->colidx) (void)hipFree(g->colidx);
-            if (g->walk_counters) (void)hipFree(g->walk_counters);
-            delete g;
-        }
-    };
-#define CSR_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t _e = (expr);                                                                    \
-        if (_e != hipSuccess) {                                                                    \
-            cleanup(true);                                                                         \
-            return set_error(EG_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));       \
-        }                                                                                          \
-    } while (0)
-    const size_t mm = (size_t)(m > 0 ? m : 1);
-    CSR_TRY(hipMalloc((void**)&keys, sizeof(int) * mm));
-    CSR_TRY(hipMalloc((void**)&vals, sizeof(int) * mm));
-    CSR_TRY(hipMalloc((void**)&keys_out, sizeof(int) * mm));
-    CSR_TRY(hipMalloc((void**)&counts, sizeof(int) * ((size_t)n + 1)));
-    CSR_TRY(hipMalloc((void**)&g->colidx, sizeof(int) * mm));
-    CSR_TRY(hipMalloc((void**)&g->rowptr, sizeof(int) * ((size_t)n + 1)));
-    CSR_TRY(hipMalloc((void**)&g->dis, sizeof(float) * (size_t)n));
-    CSR_TRY(hipMalloc((void**)&g->walk_counters, QUEUE_RING_BYTES));
-    CSR_TRY(hipMemsetAsync(g->walk_counters, 0, QUEUE_RING_BYTES, stream));
-    if (create_slot_events(g) != EG_OK) CSR_TRY(hipErrorOutOfMemory);
-    CSR_TRY(hipMemsetAsync(counts, 0, sizeof(int) * ((size_t)n + 1), stream));
-    if (m > 0) {
-        hipLaunchKernelGGL(k_edge_keys, dim3((m + 255) / 256), dim3(256), 0, stream, ei, n_edges, n, base ? 1 : 0, keys, vals, counts);
-        CSR_TRY(hipGetLastError());
-        // stable LSD radix sort by target: neighbours keep their edge_index order
-        int end_bit = 1;
-        while ((1ll << end_bit) <= n_nodes && end_bit < 32) ++end_bit;
-        CSR_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys, keys_out, vals, g->colidx, m, 0, end_bit, stream));
-    }
-    CSR_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, counts, g->rowptr, n + 1, stream));
-    if (tmp2 > tmp_bytes) tmp_bytes = tmp2;
-    CSR_TRY(hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 16));
-    if (m > 0) {
-        size_t tb = tmp_bytes;
-        int end_bit = 1;
-        while ((1ll << end_bit) <= n_nodes && end_bit < 32) ++end_bit;
-        CSR_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tb, keys, keys_out, vals, g->colidx, m, 0, end_bit, stream));
-    }
-    {
-        size_t tb = tmp_bytes;
-        CSR_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, tb, counts, g->rowptr, n + 1, stream));
-    }
-    unsigned long long sym_host[2] = {0, 0};
-    if (base) {
-        CSR_TRY(hipMemcpyAsync(g->dis, base->dis, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice, stream));
-    } else {
-        hipLaunchKernelGGL(k_dis_from_counts, dim3((n + 255) / 256), dim3(256), 0, stream, counts, n, g->dis);
-        CSR_TRY(hipGetLastError());
-        CSR_TRY(hipMalloc((void**)&sym, 2 * sizeof(unsigned long long)));
-        CSR_TRY(hipMemsetAsync(sym, 0, 2 * sizeof(unsigned long long), stream));
-        if (m > 0) {
-            int blocks = (m + 255) / 256;
-            hipLaunchKernelGGL(k_edge_sym, dim3(blocks > 2048 ? 2048 : blocks), dim3(256), 0, stream, ei, n_edges, n_nodes, sym);
-            CSR_TRY(hipGetLastError());
-        }
-        CSR_TRY(hipMemcpyAsync(sym_host, sym, sizeof(sym_host), hipMemcpyDeviceToHost, stream));
-    }
-    int nnz = 0;
-    CSR_TRY(hipMemcpyAsync(&nnz, g->rowptr + n, sizeof(int), hipMemcpyDeviceToHost, stream));
-    CSR_TRY(hipStreamSynchronize(stream));
-    g->nnz = nnz;
-    g->symmetric = base ? base->symmetric : (sym_host[0] == sym_host[1]);
-    cleanup(false);
-#undef CSR_TRY
-    if (g->knobs.csr_tiles > 0) {
-        const int rc = csr_tiles(g, g->knobs.csr_tiles, stream);
-        if (rc != EG_OK) { eg_graph_destroy(g); return rc; }
-    }
-    *out = g;
-    return EG_OK;
-}
-
 extern "C" {
 
 int eg_graph_destroy(eg_graph* g) {
-    if (!g) return EG_OK;
-    if (g->dis) (void)hipFree(g->dis);
-    if (g->topo_dev) (void)hipFree(g->topo_dev);
-    if (g->segs_dev) (void)hipFree(g->segs_dev);
-    if (g->pats_dev) (void)hipFree(g->pats_dev);
-    if (g->patsq_dev) (void)hipFree(g->patsq_dev);
-    if (g->tiles_dev) (void)hipFree(g->tiles_dev);
-    if (g->walk_counters) (void)hipFree(g->walk_counters);
-    for (int i = 0; i < eg::QUEUE_SLOTS; ++i)
-        if (g->slot_event[i]) (void)hipEventDestroy(g->slot_event[i]);
-    if (g->era_event) (void)hipEventDestroy(g->era_event);
-    if (g->rowptr) (void)hipFree(g->rowptr);
-    if (g->colidx) (void)hipFree(g->colidx);
-    if (g->conn_table) (void)hipFree(g->conn_table);
-    if (g->conn_scratch) (void)hipFree(g->conn_scratch);
-    for (float* p : g->conn_retired) (void)hipFree(p);
-    for (void* p : {(void*)g->t_rows, (void*)g->t_rowptr, (void*)g->t_code, (void*)g->t_tgt, (void*)g->t_w, (void*)g->t_dis})
-        if (p) (void)hipFree(p);
     delete g;
     return EG_OK;
 }

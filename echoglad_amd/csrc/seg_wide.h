@@ -2,7 +2,7 @@
 // Same math and paired-row register layout as stencil_row8 (tile.h), written for a 256-VGPR budget: one wave
 // handles patch rows 2p and 2p+1 of an 8x8 patch and has ALL their row loads in flight at once, so it pays one
 // memory round trip per tile.  Everything that depends only on the topology comes precomputed from the host
-// (graph.hip): run bases in a SegDesc, neighbour weights as an index into a pattern table that the kernel keeps
+// (topo_tables.hip): run bases in a SegDesc, neighbour weights as an index into a pattern table that the kernel keeps
 // in LDS in "quad" layout -- [pattern][row parity h][slot][k] = weight of (node 2k + h, slot) -- so that one
 // ds_read_b128 yields the four weights a lane needs for one neighbour class.
 #pragma once
@@ -55,7 +55,7 @@ __device__ inline f32x4 quad_w(const float* wq, int slot) { return *reinterpret_
 // segw_store overwrites afterwards) and the left / right neighbours come back as the rows one above / below, shifted by
 // the LDS address: no cross-lane VALU work (fp32 VALU and the MFMA share one issue slot per SIMD).  The
 // segment's first / last node take their outer neighbour from LR (lower half: the row left of the segment, upper half:
-// the row right of it) with the weights of SLOT_EDGE; SLOT_LEFT / SLOT_RIGHT are zero there (graph.hip).
+// the row right of it) with the weights of SLOT_EDGE; SLOT_LEFT / SLOT_RIGHT are zero there (topo_tables.hip).
 __device__ inline void segw_rows(int lane, const float* wq, const f32x4 (&S)[4], const f32x4& LR,
                                  const f32x4 (&U)[4], const f32x4 (&D)[4], const f32x4 (&P)[4], f32x4 (&acc)[4],
                                  float* s_t, int rl) {
@@ -100,7 +100,7 @@ __device__ inline void segw_rows(int lane, const float* wq, const f32x4 (&S)[4],
 // ---- two vertically adjacent segments (patch rows 2p, 2p+1) handled by one wave ----------------------------------
 // The rows below segment a ARE segment b and the rows above b are a; both share their 4 parents, and the two edge
 // rows of a segment come in one load: 22 wave loads instead of 32.  SegDesc::pad0 of the upper segment says when this
-// holds (host, graph.hip).
+// holds (host, topo_tables.hip).
 struct SegPair {
     f32x4 Sa[4], Sb[4], LRa, LRb, U[4], D[4], P[4];   // LR: lower half = row left of the segment, upper half = row right of it
 };
@@ -127,7 +127,7 @@ __device__ inline void segp_issue(const SegDesc& sa, const SegDesc& sb, const Ro
 // pair's own two rows, the row above, the row below -- goes through LDS scaled, and a target adds the entries one to the
 // left, at and one to the right of its column ("sum3").  What lies outside the segment comes from the edge rows (one load per
 // row set: left edge in the lower half-wave, right edge in the upper), whose weights are zero where the grid ends.  Pattern
-// slots of a diagonal segment (graph.hip): SELF / UP / DOWN = d of the node itself / above / below, EDGE = own row's edge
+// slots of a diagonal segment (topo_tables.hip): SELF / UP / DOWN = d of the node itself / above / below, EDGE = own row's edge
 // nodes, slots 3 / 4 (LEFT / RIGHT on plain levels) = the edge nodes of the row above / below.
 constexpr int SLOT_EDGE_U = SLOT_LEFT, SLOT_EDGE_D = SLOT_RIGHT;
 constexpr int SEG_AUX_DIAG = 2;                       // SegDesc::aux bit 1: the segment's level is 'grid-diagonal'

@@ -1,6 +1,6 @@
 // Host-side check of the C ABI under AddressSanitizer + UBSan (CPU only; built and run by tests/test_abi_sanitized.py).
 // Drives what the library does on the HOST: argument validation of the entry points and the topology-table construction of
-// eg_topo_create (closed-form level / tile / segment / weight-pattern tables, graph.hip), whose indexing is where a host-side
+// eg_topo_create (closed-form level / tile / segment / weight-pattern tables, topo_tables.hip), whose indexing is where a host-side
 // out-of-bounds would hide.  Without a GPU the device allocation at the end of eg_topo_create fails and the error path frees
 // everything; with one the handle is created and destroyed.  Exit code 0 = every call returned what it should and the
 // sanitizers stayed silent (they abort the process otherwise).
