@@ -14,26 +14,9 @@
 // Every output element is a chain of fused multiply-adds in a fixed order (input channel ascending, tap ascending; the deep kernel
 // adds its 16 chains in wave order): no atomics, the same bits on every run.  Nothing is allocated and nothing waits for the host.
 #include "common.h"
+#include "frontend.h"
 
 namespace eg {
-
-constexpr int FE_MAX_SIDE = 512;
-constexpr int FE_MAX_CH = 512;
-constexpr int FE_DEEP_MAX_SIDE = 16;      // sides up to this one take k_conv3x3_deep
-
-struct FeConv {
-    const float* x0;        // [batch, c0, side0, side0], nearest-resized to side
-    const float* x1;        // [batch, c1, side, side] or NULL
-    const float* weight;    // [c_out, c0 + c1, 3, 3]
-    const float* bias;      // [c_out] or NULL
-    const float* gamma;     // [c_out] or NULL (1)
-    const float* beta;      // [c_out] or NULL (0)
-    const float* mean;      // [c_out]
-    const float* var;       // [c_out]
-    float* out;             // [batch, c_out, side, side]
-    float eps;
-    int c0, c1, c_out, batch, side, side0;
-};
 
 // out = (relu(acc + bias) - mean) * (gamma / sqrt(var + eps)) + beta of output channel o
 __device__ inline float fe_epilogue(const FeConv& A, int o, float acc) {
@@ -42,10 +25,26 @@ __device__ inline float fe_epilogue(const FeConv& A, int o, float acc) {
     return (r - A.mean[o]) * k + (A.beta ? A.beta[o] : 0.f);
 }
 
-// nearest resize: the source row / column of destination d (nn.Upsample(size=side) on a side0 map)
-__device__ inline int fe_src(int d, int side0, int side) {
-    const int s = (d * side0) / side;              // d < 512, side0 <= 512: no overflow
-    return s < side0 - 1 ? s : side0 - 1;
+// the nine taps of (output channel oc, input channel c) of the launch: W[oc][c] in place, or, for the data gradient (whose output
+// channels are the convolution's INPUT channels, c_out of them, and whose taps run backwards), W[c][oc]; contiguous either way
+template <int MODE>
+__device__ inline const float* fe_taps(const FeConv& A, int oc, int c, int c_in) {
+    return A.weight + (MODE == FE_DGRAD ? (size_t)c * A.c_out + oc : (size_t)oc * c_in + c) * 9;
+}
+
+// what one finished chain becomes, and where it goes: the eval epilogue, relu(acc + bias) (the train forward's r), or the plain sum
+// split at channel `split` into the gradients of the two sources (either may be absent)
+template <int MODE>
+__device__ inline void fe_store(const FeConv& A, int b, int o, int plane, int r, float acc) {
+    if (MODE == FE_EVAL) {
+        A.out[((size_t)b * A.c_out + o) * plane + r] = fe_epilogue(A, o, acc);
+    } else if (MODE == FE_RELU) {
+        A.out[((size_t)b * A.c_out + o) * plane + r] = fmaxf(acc + (A.bias ? A.bias[o] : 0.f), 0.f);
+    } else if (o < A.split) {
+        if (A.out) A.out[((size_t)b * A.split + o) * plane + r] = acc;
+    } else if (A.out1) {
+        A.out1[((size_t)b * (A.c_out - A.split) + o - A.split) * plane + r] = acc;
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -58,7 +57,7 @@ constexpr int FT_POS = FT_LW * FT_LH;                    // 340 positions with t
 constexpr int FT_PER = (FT_POS + FT_THREADS - 1) / FT_THREADS;      // positions a thread stages: 2
 constexpr int FT_CIB = 8;                                // input channels per LDS stage
 
-template <int OCB>
+template <int OCB, int MODE>
 __global__ __launch_bounds__(FT_THREADS) void k_conv3x3_tile(const FeConv A, int tiles_x) {
     __shared__ float s_in[FT_CIB][FT_POS];
     const int t = threadIdx.x;
@@ -112,9 +111,9 @@ __global__ __launch_bounds__(FT_THREADS) void k_conv3x3_tile(const FeConv A, int
 #pragma unroll
             for (int o = 0; o < OCB; ++o) {
                 const int oc = o0 + o < A.c_out ? o0 + o : A.c_out - 1;            // wave-uniform: scalar loads
-                const float* w = A.weight + ((size_t)oc * c_in + cb + ci) * 9;
+                const float* w = fe_taps<MODE>(A, oc, cb + ci, c_in);
 #pragma unroll
-                for (int k = 0; k < 9; ++k) acc[o] = fmaf(v[k], w[k], acc[o]);
+                for (int k = 0; k < 9; ++k) acc[o] = fmaf(v[k], w[MODE == FE_DGRAD ? 8 - k : k], acc[o]);
             }
         }
         __syncthreads();
@@ -125,7 +124,7 @@ __global__ __launch_bounds__(FT_THREADS) void k_conv3x3_tile(const FeConv A, int
 #pragma unroll
         for (int o = 0; o < OCB; ++o)
             if (o0 + o < A.c_out)
-                A.out[((size_t)b * A.c_out + o0 + o) * plane + y * side + x] = fe_epilogue(A, o0 + o, acc[o]);
+                fe_store<MODE>(A, b, o0 + o, plane, y * side + x, acc[o]);
     }
 }
 
@@ -138,9 +137,9 @@ constexpr int FD_OCW = 4;                                // output channels per 
 
 // input channels [lo, hi) of one source into acc: the lane's 9 taps come straight from global memory (the maps are a few KB per
 // channel and stay in L1 / L2), an out-of-map tap loads the centre instead and is replaced by 0
-__device__ inline void fd_accumulate(const float* __restrict__ src, int plane_src, const int (&off)[9], unsigned ok,
-                                     const float* __restrict__ weight, int c_in, int c_shift, int lo, int hi, int o0, int c_out,
-                                     float (&acc)[FD_OCW]) {
+template <int MODE>
+__device__ inline void fd_accumulate(const float* __restrict__ src, int plane_src, const int (&off)[9], unsigned ok, const FeConv& A,
+                                     int c_in, int c_shift, int lo, int hi, int o0, float (&acc)[FD_OCW]) {
 #pragma unroll 2
     for (int c = lo; c < hi; ++c) {
         float v[9];
@@ -151,14 +150,15 @@ __device__ inline void fd_accumulate(const float* __restrict__ src, int plane_sr
         }
 #pragma unroll
         for (int o = 0; o < FD_OCW; ++o) {
-            const int oc = o0 + o < c_out ? o0 + o : c_out - 1;                    // wave-uniform: scalar loads
-            const float* w = weight + ((size_t)oc * c_in + c) * 9;
+            const int oc = o0 + o < A.c_out ? o0 + o : A.c_out - 1;                // wave-uniform: scalar loads
+            const float* w = fe_taps<MODE>(A, oc, c, c_in);
 #pragma unroll
-            for (int k = 0; k < 9; ++k) acc[o] = fmaf(v[k], w[k], acc[o]);
+            for (int k = 0; k < 9; ++k) acc[o] = fmaf(v[k], w[MODE == FE_DGRAD ? 8 - k : k], acc[o]);
         }
     }
 }
 
+template <int MODE>
 __global__ __launch_bounds__(FD_THREADS) void k_conv3x3_deep(const FeConv A, int total_px) {
     __shared__ float s_red[FD_WAVES][FD_OCW][64];
     const int lane = threadIdx.x & 63;
@@ -192,9 +192,9 @@ __global__ __launch_bounds__(FD_THREADS) void k_conv3x3_deep(const FeConv A, int
     const int per = (c_in + FD_WAVES - 1) / FD_WAVES;
     const int lo = wave * per, hi = lo + per < c_in ? lo + per : c_in;
     // [lo, hi) splits at c0 into the part of x0 and the part of x1
-    fd_accumulate(A.x0 + (size_t)b * c0 * plane0, plane0, off0, ok, A.weight, c_in, 0, lo, hi < c0 ? hi : c0, o0, A.c_out, acc);
+    fd_accumulate<MODE>(A.x0 + (size_t)b * c0 * plane0, plane0, off0, ok, A, c_in, 0, lo, hi < c0 ? hi : c0, o0, acc);
     if (A.x1)
-        fd_accumulate(A.x1 + (size_t)b * A.c1 * plane, plane, off1, ok, A.weight, c_in, c0, lo > c0 ? lo : c0, hi, o0, A.c_out, acc);
+        fd_accumulate<MODE>(A.x1 + (size_t)b * A.c1 * plane, plane, off1, ok, A, c_in, c0, lo > c0 ? lo : c0, hi, o0, acc);
 
 #pragma unroll
     for (int o = 0; o < FD_OCW; ++o) s_red[wave][o][lane] = acc[o];
@@ -203,7 +203,7 @@ __global__ __launch_bounds__(FD_THREADS) void k_conv3x3_deep(const FeConv A, int
         float sum = s_red[0][wave][lane];
 #pragma unroll
         for (int w = 1; w < FD_WAVES; ++w) sum += s_red[w][wave][lane];
-        A.out[((size_t)b * A.c_out + o0 + wave) * plane + r] = fe_epilogue(A, o0 + wave, sum);
+        fe_store<MODE>(A, b, o0 + wave, plane, r, sum);
     }
 }
 
@@ -232,6 +232,47 @@ __global__ __launch_bounds__(FP_THREADS) void k_adaptive_max_pool(const float* _
     out[e] = m;
 }
 
+template <int MODE>
+static int fe_launch_mode(const FeConv& A, hipStream_t stream) {
+    const long long total_px = (long long)A.batch * A.side * A.side;
+    const int side = A.side, c_out = A.c_out, batch = A.batch;
+    if (side <= FE_DEEP_MAX_SIDE) {
+        const dim3 grid((unsigned)((total_px + 63) / 64), (unsigned)((c_out + FD_OCW - 1) / FD_OCW));
+        hipLaunchKernelGGL(k_conv3x3_deep<MODE>, grid, dim3(FD_THREADS), 0, stream, A, (int)total_px);
+    } else {
+        const int tiles_x = (side + FT_W - 1) / FT_W, tiles_y = (side + FT_H - 1) / FT_H;
+        // 8 output channels per lane halve the LDS reads per multiply-add; 4 where that would leave most of the chip without a tile
+        const bool wide = c_out >= 8 && (long long)tiles_x * tiles_y * ((c_out + 7) / 8) * batch >= 512;
+        if (wide)
+            hipLaunchKernelGGL((k_conv3x3_tile<8, MODE>), dim3(tiles_x * tiles_y, (c_out + 7) / 8, batch), dim3(FT_THREADS), 0,
+                               stream, A, tiles_x);
+        else
+            hipLaunchKernelGGL((k_conv3x3_tile<4, MODE>), dim3(tiles_x * tiles_y, (c_out + 3) / 4, batch), dim3(FT_THREADS), 0,
+                               stream, A, tiles_x);
+    }
+    EG_HIP_TRY(hipGetLastError());
+    return EG_OK;
+}
+
+int fe_check_shapes(int batch, int c0, int c1, int c_out, int side, int side0) {
+    if (batch < 1) return set_error(EG_ERR_ARG, "batch must be >= 1");
+    if (c0 < 1 || c1 < 0 || c_out < 1) return set_error(EG_ERR_ARG, "c0 and c_out must be >= 1, c1 >= 0");
+    if (side < 1 || side0 < 1) return set_error(EG_ERR_ARG, "side and side0 must be >= 1");
+    if (c0 > FE_MAX_CH || c1 > FE_MAX_CH || c0 + c1 > FE_MAX_CH || c_out > FE_MAX_CH)
+        return set_error(EG_ERR_UNSUPPORTED, "channels (c0 + c1, c_out) above 512 are not covered");
+    if (side > FE_MAX_SIDE || side0 > FE_MAX_SIDE) return set_error(EG_ERR_UNSUPPORTED, "sides above 512 are not covered");
+    if (batch > 65535 || (long long)batch * side * side >= (1ll << 31))
+        return set_error(EG_ERR_UNSUPPORTED, "batch too large for one launch");
+    return EG_OK;
+}
+
+// the one launcher of both convolution kernels: the caller has checked A (fe_check_shapes)
+int fe_launch_conv(const FeConv& A, int mode, hipStream_t stream) {
+    if (mode == FE_EVAL) return fe_launch_mode<FE_EVAL>(A, stream);
+    if (mode == FE_RELU) return fe_launch_mode<FE_RELU>(A, stream);
+    return fe_launch_mode<FE_DGRAD>(A, stream);
+}
+
 }  // namespace eg
 
 using namespace eg;
@@ -243,34 +284,12 @@ int eg_conv3x3_relu_bn_fwd(const float* x0, int c0, int side0, const float* x1, 
                            const float* bn_var, float bn_eps, int c_out, float* out, eg_stream_t stream) {
     if (!x0 || !weight || !bn_mean || !bn_var || !out)
         return set_error(EG_ERR_ARG, "x0, weight, bn_mean, bn_var and out must not be NULL");
-    if (batch < 1) return set_error(EG_ERR_ARG, "batch must be >= 1");
-    if (c0 < 1 || c1 < 0 || c_out < 1) return set_error(EG_ERR_ARG, "c0 and c_out must be >= 1, c1 >= 0");
-    if (side < 1 || side0 < 1) return set_error(EG_ERR_ARG, "side and side0 must be >= 1");
     if ((c1 > 0) != (x1 != nullptr)) return set_error(EG_ERR_ARG, "x1 must be given exactly when c1 > 0");
     if (!(bn_eps >= 0.f)) return set_error(EG_ERR_ARG, "bn_eps must be >= 0");
     if (out == x0 || out == x1) return set_error(EG_ERR_ARG, "out must not alias an input");
-    if (c0 > FE_MAX_CH || c1 > FE_MAX_CH || c0 + c1 > FE_MAX_CH || c_out > FE_MAX_CH)
-        return set_error(EG_ERR_UNSUPPORTED, "channels (c0 + c1, c_out) above 512 are not covered");
-    if (side > FE_MAX_SIDE || side0 > FE_MAX_SIDE) return set_error(EG_ERR_UNSUPPORTED, "sides above 512 are not covered");
-    const long long total_px = (long long)batch * side * side;
-    if (batch > 65535 || total_px >= (1ll << 31)) return set_error(EG_ERR_UNSUPPORTED, "batch too large for one launch");
-    FeConv A{x0, x1, weight, bias, bn_weight, bn_bias, bn_mean, bn_var, out, bn_eps, c0, c1, c_out, batch, side, side0};
-    if (side <= FE_DEEP_MAX_SIDE) {
-        const dim3 grid((unsigned)((total_px + 63) / 64), (unsigned)((c_out + FD_OCW - 1) / FD_OCW));
-        hipLaunchKernelGGL(k_conv3x3_deep, grid, dim3(FD_THREADS), 0, (hipStream_t)stream, A, (int)total_px);
-    } else {
-        const int tiles_x = (side + FT_W - 1) / FT_W, tiles_y = (side + FT_H - 1) / FT_H;
-        // 8 output channels per lane halve the LDS reads per multiply-add; 4 where that would leave most of the chip without a tile
-        const bool wide = c_out >= 8 && (long long)tiles_x * tiles_y * ((c_out + 7) / 8) * batch >= 512;
-        if (wide)
-            hipLaunchKernelGGL(k_conv3x3_tile<8>, dim3(tiles_x * tiles_y, (c_out + 7) / 8, batch), dim3(FT_THREADS), 0,
-                               (hipStream_t)stream, A, tiles_x);
-        else
-            hipLaunchKernelGGL(k_conv3x3_tile<4>, dim3(tiles_x * tiles_y, (c_out + 3) / 4, batch), dim3(FT_THREADS), 0,
-                               (hipStream_t)stream, A, tiles_x);
-    }
-    EG_HIP_TRY(hipGetLastError());
-    return EG_OK;
+    if (const int rc = fe_check_shapes(batch, c0, c1, c_out, side, side0)) return rc;
+    FeConv A{x0, x1, weight, bias, bn_weight, bn_bias, bn_mean, bn_var, out, bn_eps, c0, c1, c_out, batch, side, side0, nullptr, 0};
+    return fe_launch_conv(A, FE_EVAL, (hipStream_t)stream);
 }
 
 int eg_adaptive_max_pool_fwd(const float* x, int planes, int side_in, int side_out, float* out, eg_stream_t stream) {

@@ -3,7 +3,8 @@
 ``UNetNodeFeatureModel`` has the shape of the reference's ``UNETHierarchicalPatchModel`` (src/core/models.py:639-756; the class
 ``configs/default.yml`` names as ``unet_hierarchical_patch``): a convolutional encoder / decoder in front of the GNN whose
 decoder maps become the node features of the levels.  The front-end is dense convolution work, written here with plain torch
-modules (MIOpen) for training; ``enable_hip_frontend()`` switches its eval-mode forward to the HIP front-end (frontend.hip).  The
+modules (MIOpen); ``enable_hip_frontend()`` switches its eval-mode forward to the HIP front-end (frontend.hip), and with
+``train=True`` its training-mode forward and backward as well (frontend_train.hip).  The
 HIP path that is always on begins at the tail of ``create_node_pixels``, where the reference applies a 1x1 convolution + ReLU to
 every decoder map and concatenates the permuted maps per sample in a Python loop (models.py:707-756).  That tail is ONE launch
 here (``pack_node_features_linear`` -> eg_conv1x1_relu_pack_levels) and writes the GNN's input layout directly; everything
@@ -19,7 +20,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .nn import C, HierarchicalPatchModel, unet_decoder_maps
+from .nn import C, HierarchicalPatchModel, unet_decoder_maps, unet_decoder_maps_train
 from .topology import get_topology
 
 
@@ -73,18 +74,24 @@ class UNetNodeFeatureModel(HierarchicalPatchModel):
         self.up_convs = nn.ModuleList(_Up(d, d // 2, s) for d, s in zip(reversed(dims), up_sides))
         feats_in = list(reversed(dims)) + [dims[0] // 2]
         self.linears = nn.ModuleList(nn.Conv2d(c, self.node_embedding_dim, kernel_size=1) for c in feats_in)
-        self.hip_frontend = False           # a plain attribute: no parameter, no buffer, not in the state_dict
+        self.hip_frontend = False           # plain attributes: no parameter, no buffer, not in the state_dict
+        self.hip_frontend_train = False
 
-    def enable_hip_frontend(self, flag: bool = True) -> "UNetNodeFeatureModel":
+    def enable_hip_frontend(self, flag: bool = True, train: bool = False) -> "UNetNodeFeatureModel":
         """Opt in: in eval mode with autograd off, ``decoder_maps`` runs on the HIP front-end (``nn.unet_decoder_maps``: 35
-        launches, bit-reproducible) instead of torch's modules.  Training and eval with gradients keep the torch path."""
+        launches, bit-reproducible) instead of torch's modules.  Training and eval with gradients keep the torch path, unless
+        ``train=True``: then training mode with autograd on takes ``nn.unet_decoder_maps_train`` (batch statistics, HIP backward,
+        bit-reproducible); eval with gradients stays on torch."""
         self.hip_frontend = bool(flag)
+        self.hip_frontend_train = bool(flag) and bool(train)
         return self
 
     def decoder_maps(self, frames: torch.Tensor) -> List[torch.Tensor]:
         """[B, dims[0] // 2, F, F] -> the decoder's maps, coarse to fine: sides 2, 4, ..., 2^naux, F."""
         if self.hip_frontend and not self.training and not torch.is_grad_enabled():
             return unet_decoder_maps(self.down_convs, self.up_convs, frames)
+        if self.hip_frontend_train and self.training and torch.is_grad_enabled():
+            return unet_decoder_maps_train(self.down_convs, self.up_convs, frames)
         x, skips = frames, []
         for down in self.down_convs:
             skips.append(x)

@@ -89,8 +89,10 @@ extern "C" {
  * 136: eg_classifier_train_fwd_act(h_sparse), eg_classifier_bwd_sums(layer_residual, recompute_h).  137, 138: eg_coord_update_fwd / _bwd.  139, 140: eg_adam_step.
  * 141: eg_confusion_counts.  142: eg_bce_probs_fwd / _bwd, eg_criteria_ex_fwd / _bwd.
  * 143: eg_landmark_record_workspace_bytes, eg_landmark_record_hm, eg_landmark_record_coord.  144: eg_node_labels.
- * 145: eg_conv3x3_relu_bn_fwd, eg_adaptive_max_pool_fwd. */
-#define EG_ABI_VERSION 145
+ * 145: eg_conv3x3_relu_bn_fwd, eg_adaptive_max_pool_fwd.
+ * 146: eg_frontend_train_workspace_bytes, eg_conv3x3_relu_fwd, eg_bn2d_train_fwd, eg_relu_bn2d_bwd, eg_conv3x3_bwd_data,
+ * eg_conv3x3_bwd_weight, eg_adaptive_max_pool_idx_fwd, eg_adaptive_max_pool_bwd. */
+#define EG_ABI_VERSION 146
 
 #define EG_CHANNELS 128 /* node_embedding_dim == node_hidden_dim (configs/default.yml:13-14) */
 
@@ -688,6 +690,44 @@ int eg_conv3x3_relu_bn_fwd(const float* x0, int c0, int side0, const float* x1, 
                            const float* bias, const float* bn_weight, const float* bn_bias, const float* bn_mean,
                            const float* bn_var, float bn_eps, int c_out, float* out, eg_stream_t stream);
 int eg_adaptive_max_pool_fwd(const float* x, int planes, int side_in, int side_out, float* out, eg_stream_t stream);
+
+/* ---- UNet front-end, training (the same block with batch statistics, and its backward) ----------------------------------------
+ * One conv3x3 -> ReLU -> BatchNorm2d block in training mode is eg_conv3x3_relu_fwd + eg_bn2d_train_fwd (3 launches); its backward is
+ * eg_relu_bn2d_bwd, eg_conv3x3_bwd_data and eg_conv3x3_bwd_weight (up to 7).  Sources, layouts and limits are the forward's above.
+ * workspace: device memory of eg_frontend_train_workspace_bytes(batch, c0 + c1, c_out, side) bytes (0: shapes out of range), owned by
+ * the caller, shared by the calls of one block on one stream.
+ * eg_conv3x3_relu_fwd:  r[b, o] = relu(bias[o] + conv3x3(input)[b, o]) -- the eval kernels with another epilogue.
+ * eg_bn2d_train_fwd:    per channel, mean and biased variance over n = batch side^2 values of r;
+ *     y = (r - mean) * gamma / sqrt(var + eps) + beta, save_mean = mean, save_invstd = 1 / sqrt(var + eps),
+ *     running_mean = (1 - momentum) running_mean + momentum mean, running_var likewise with var n / (n - 1); both may be NULL.
+ *     gamma, beta may be NULL (1, 0).  n == 1 is refused (EG_ERR_ARG) with torch's message.
+ * eg_relu_bn2d_bwd:     dbeta = sum dy, dgamma = sum dy xhat (xhat = (r - save_mean) save_invstd),
+ *     dz = gamma save_invstd (dy - dbeta / n - xhat dgamma / n) [r > 0], dbias = sum dz.  dgamma, dbeta, dbias [channels] may be NULL.
+ * eg_conv3x3_bwd_data:  d input = conv3x3(dz, weight transposed, taps flipped); channels >= c0 go to dx1 [batch, c1, side, side],
+ *     channels < c0 to dx0 [batch, c0, side0, side0]: where side0 != side every source pixel adds the destination pixels that read it
+ *     (src = min(dst * side0 / side, side0 - 1)) in row-major order out of `full` [batch, c0, side, side], scratch the caller brings.
+ *     dx0 or dx1 may be NULL (not wanted); enlargements above 16 x are EG_ERR_UNSUPPORTED for dx0.
+ * eg_conv3x3_bwd_weight: dweight[o][c][ky][kx] = sum_{b, y, x} dz[b, o, y, x] input[b, c, y + ky - 1, x + kx - 1] (zero padding).
+ * eg_adaptive_max_pool_idx_fwd: eg_adaptive_max_pool_fwd that also writes idx [planes, side_out, side_out], the offset y * side_in + x
+ *     of the window's first maximum in row-major order (a NaN always takes over: torch's rule).
+ * eg_adaptive_max_pool_bwd: dx [planes, side_in, side_in]: every input pixel adds dy of the windows whose idx it is, in window order.
+ * All: the caller's stream, no allocation, no synchronisation, no atomics; every sum has a fixed order in chains of at most 256
+ * terms (bit-identical from run to run), capturable.  EG_ERR_ARG / EG_ERR_UNSUPPORTED as for the forward, nothing launched. */
+size_t eg_frontend_train_workspace_bytes(int batch, int c_in, int c_out, int side);
+int eg_conv3x3_relu_fwd(const float* x0, int c0, int side0, const float* x1, int c1, int batch, int side, const float* weight,
+                        const float* bias, int c_out, float* r, eg_stream_t stream);
+int eg_bn2d_train_fwd(const float* r, int batch, int channels, int side, const float* gamma, const float* beta, float eps,
+                      float momentum, float* running_mean, float* running_var, void* workspace, float* y, float* save_mean,
+                      float* save_invstd, eg_stream_t stream);
+int eg_relu_bn2d_bwd(const float* dy, const float* r, const float* save_mean, const float* save_invstd, const float* gamma, int batch,
+                     int channels, int side, void* workspace, float* dz, float* dgamma, float* dbeta, float* dbias,
+                     eg_stream_t stream);
+int eg_conv3x3_bwd_data(const float* dz, const float* weight, int batch, int c_out, int side, int c0, int side0, int c1, float* dx0,
+                        float* dx1, float* full, eg_stream_t stream);
+int eg_conv3x3_bwd_weight(const float* x0, int c0, int side0, const float* x1, int c1, int batch, int side, const float* dz, int c_out,
+                          void* workspace, float* dweight, eg_stream_t stream);
+int eg_adaptive_max_pool_idx_fwd(const float* x, int planes, int side_in, int side_out, float* out, int* idx, eg_stream_t stream);
+int eg_adaptive_max_pool_bwd(const float* dy, const int* idx, int planes, int side_in, int side_out, float* dx, eg_stream_t stream);
 
 /* ---- node-feature packing (the step right before the hot path) -------------------------------------------
  * Reference: the per-sample loops at the tail of create_node_pixels (src/core/models.py:498-537, :590-636,

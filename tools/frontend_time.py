@@ -1,10 +1,15 @@
 """UNet front-end at 224/7, default dims: torch modules (MIOpen) against the HIP front-end (enable_hip_frontend), on one device.
 
     python tools/frontend_time.py [batch]            (GPU box; under rocprofv3 --kernel-trace --stats for per-launch times)
+    python tools/frontend_time.py train              the training leg: forward + backward of `decoder_maps` at batch 1 and 8
 
 Three interleaved pairs (off, on, off, on, off, on) of `decoder_maps` and of frame -> logits (`model(x=..., edge_index=...)`), each
 a host clock around ITERS calls that ends in a device synchronise, after a warm-up of every shape.  Prints one line per pair and
-a JSON summary line; exits non-zero if the two routes' maps differ by more than 1e-3 of the map's largest value."""
+a JSON summary line; exits non-zero if the two routes' maps differ by more than 1e-3 of the map's largest value.
+
+The training leg times forward + backward (loss = the sum of every map) of `decoder_maps` in training mode with
+enable_hip_frontend(True, train=False) -- torch modules (MIOpen), what the parent of the training route ran -- against train=True
+(frontend_train.hip), again in three interleaved pairs per batch size on one device, and prints one JSON line.  No gate."""
 import json
 import os
 import subprocess
@@ -30,7 +35,43 @@ def timed(fn):
     return (time.perf_counter() - t0) / ITERS * 1e3          # ms per call
 
 
+def train_leg():
+    assert torch.cuda.is_available(), "frontend_time.py measures on a GPU"
+    dev = "cuda:0"
+    torch.manual_seed(0)
+    model = UNetNodeFeatureModel(frame_size=224, num_aux_graphs=7, node_embedding_dim=128, node_hidden_dim=128, classifier_hidden_dim=32,
+                                 num_gnn_layers=3, output_activation="logit", use_coordinate_graph=False, gnn_dropout_p=0.5,
+                                 classifier_dropout_p=0.5).to(dev).train()
+    params = list(model.down_convs.parameters()) + list(model.up_convs.parameters())
+    result = {"tool": "frontend_time", "leg": "train", "device": torch.cuda.get_device_name(0), "iters": ITERS, "batches": {}}
+    for B in (1, 8):
+        frames = torch.randn(B, 4, 224, 224, device=dev)
+
+        def step():
+            for p in params:
+                p.grad = None
+            sum(m.sum() for m in model.decoder_maps(frames)).backward()
+
+        ms = {"torch": [], "hip": []}
+        for name in ms:                                     # warm-up of both routes
+            model.enable_hip_frontend(True, train=name == "hip")
+            for _ in range(WARMUP):
+                step()
+        for pair in range(PAIRS):
+            for name in ms:
+                model.enable_hip_frontend(True, train=name == "hip")
+                ms[name].append(timed(step))
+            print(f"train, batch {B}, pair {pair}: forward + backward torch {ms['torch'][-1]:.3f} ms, hip {ms['hip'][-1]:.3f} ms "
+                  f"({ms['torch'][-1] / ms['hip'][-1]:.2f}x)", flush=True)
+        result["batches"][str(B)] = {"fwd_bwd_ms_torch": ms["torch"], "fwd_bwd_ms_hip": ms["hip"],
+                                     "hip_faster_in_every_pair": all(a > b for a, b in zip(ms["torch"], ms["hip"]))}
+    print(json.dumps(result))
+    return 0
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "train":
+        return train_leg()
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
     assert torch.cuda.is_available(), "frontend_time.py measures on a GPU"
     dev = "cuda:0"
