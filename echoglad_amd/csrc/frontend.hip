@@ -1,8 +1,9 @@
 // The UNet front-end of the reference's unet_hierarchical_patch model in eval mode (src/core/models.py:639-756; DownConv :841-856,
 // UpConv :859-876): conv3x3 (zero padding 1) -> ReLU -> BatchNorm with running statistics as ONE launch, whose input is the
 // channel concatenation of a nearest-resized map and an optional second map (so nn.Upsample and torch.cat never materialise), and
-// nn.AdaptiveMaxPool2d.  fp32 NCHW throughout; weights are read in torch's own [c_out, c_in, 3, 3] layout, in place, every call:
-// there is no cached re-layout and no cached folded parameter that could go stale.
+// nn.AdaptiveMaxPool2d (the kernel is frontend.h's: the training mode runs it too).  fp32 NCHW throughout; weights are read in
+// torch's own [c_out, c_in, 3, 3] layout, in place, every call: there is no cached re-layout and no cached folded parameter that
+// could go stale.
 //
 // Two kernels serve the convolution:
 //   k_conv3x3_tile   side > 16: many pixels, few channels.  A workgroup owns a 32 x 8 pixel tile and OCB output channels of one
@@ -207,31 +208,6 @@ __global__ __launch_bounds__(FD_THREADS) void k_conv3x3_deep(const FeConv A, int
     }
 }
 
-// ---------------------------------------------------------------------------
-// nn.AdaptiveMaxPool2d: one thread per output element, window [floor(i in / out), ceil((i + 1) in / out))
-// ---------------------------------------------------------------------------
-constexpr int FP_THREADS = 256;
-
-__global__ __launch_bounds__(FP_THREADS) void k_adaptive_max_pool(const float* __restrict__ x, long long total, int side_in,
-                                                                  int side_out, float* __restrict__ out) {
-    const long long e = (long long)blockIdx.x * FP_THREADS + threadIdx.x;
-    if (e >= total) return;
-    const int plane_out = side_out * side_out;
-    const long long pl = e / plane_out;
-    const int r = (int)(e - pl * plane_out);
-    const int i = r / side_out, j = r - i * side_out;
-    const int y0 = (i * side_in) / side_out, y1 = ((i + 1) * side_in + side_out - 1) / side_out;
-    const int x0 = (j * side_in) / side_out, x1 = ((j + 1) * side_in + side_out - 1) / side_out;
-    const float* src = x + pl * side_in * side_in;
-    float m = -INFINITY;
-    for (int yy = y0; yy < y1; ++yy)
-        for (int xx = x0; xx < x1; ++xx) {
-            const float v = src[yy * side_in + xx];
-            if (v > m || v != v) m = v;                  // torch's rule: a NaN in the window is the result
-        }
-    out[e] = m;
-}
-
 template <int MODE>
 static int fe_launch_mode(const FeConv& A, hipStream_t stream) {
     const long long total_px = (long long)A.batch * A.side * A.side;
@@ -284,28 +260,22 @@ int eg_conv3x3_relu_bn_fwd(const float* x0, int c0, int side0, const float* x1, 
                            const float* bn_var, float bn_eps, int c_out, float* out, eg_stream_t stream) {
     if (!x0 || !weight || !bn_mean || !bn_var || !out)
         return set_error(EG_ERR_ARG, "x0, weight, bn_mean, bn_var and out must not be NULL");
-    if ((c1 > 0) != (x1 != nullptr)) return set_error(EG_ERR_ARG, "x1 must be given exactly when c1 > 0");
+    if (const int rc = fe_check_x1(x1, c1)) return rc;
     if (!(bn_eps >= 0.f)) return set_error(EG_ERR_ARG, "bn_eps must be >= 0");
     if (out == x0 || out == x1) return set_error(EG_ERR_ARG, "out must not alias an input");
     if (const int rc = fe_check_shapes(batch, c0, c1, c_out, side, side0)) return rc;
-    FeConv A{x0, x1, weight, bias, bn_weight, bn_bias, bn_mean, bn_var, out, bn_eps, c0, c1, c_out, batch, side, side0, nullptr, 0};
+    FeConv A;
+    A.x0 = x0; A.x1 = x1; A.weight = weight; A.bias = bias; A.out = out;
+    A.gamma = bn_weight; A.beta = bn_bias; A.mean = bn_mean; A.var = bn_var; A.eps = bn_eps;
+    A.c0 = c0; A.c1 = c1; A.c_out = c_out; A.batch = batch; A.side = side; A.side0 = side0;
     return fe_launch_conv(A, FE_EVAL, (hipStream_t)stream);
 }
 
 int eg_adaptive_max_pool_fwd(const float* x, int planes, int side_in, int side_out, float* out, eg_stream_t stream) {
-    if (!x || !out) return set_error(EG_ERR_ARG, "x and out must not be NULL");
-    if (planes < 1) return set_error(EG_ERR_ARG, "planes must be >= 1");
-    if (side_out < 1 || side_in < 1) return set_error(EG_ERR_ARG, "side_in and side_out must be >= 1");
-    if (side_out > side_in) return set_error(EG_ERR_ARG, "side_out must not exceed side_in");
-    if (side_in > FE_MAX_SIDE) return set_error(EG_ERR_UNSUPPORTED, "sides above 512 are not covered");
+    if (const int rc = fe_pool_check(x, out, "x and out must not be NULL", planes, side_in, side_out)) return rc;
     if (out == x) return set_error(EG_ERR_ARG, "out must not alias x");
-    const long long total = (long long)planes * side_out * side_out;
-    const long long blocks = (total + FP_THREADS - 1) / FP_THREADS;
-    if (blocks >= (1ll << 31)) return set_error(EG_ERR_UNSUPPORTED, "planes * side_out^2 too large for one launch");
-    hipLaunchKernelGGL(k_adaptive_max_pool, dim3((unsigned)blocks), dim3(FP_THREADS), 0, (hipStream_t)stream, x, total, side_in,
-                       side_out, out);
-    EG_HIP_TRY(hipGetLastError());
-    return EG_OK;
+    if (fe_pool_too_large(planes, side_out)) return set_error(EG_ERR_UNSUPPORTED, "planes * side_out^2 too large for one launch");
+    return fe_pool_forward<false>(x, planes, side_in, side_out, out, nullptr, (hipStream_t)stream);
 }
 
 }  // extern "C"

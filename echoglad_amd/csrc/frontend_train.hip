@@ -1,7 +1,8 @@
 // The UNet front-end in TRAINING mode: conv3x3 -> ReLU -> BatchNorm2d with batch statistics, its backward, and the
-// adaptive max pool with its backward.  fp32 NCHW; the convolution's input is the forward's (x0 nearest-resized, concatenated with
-// an optional x1) and is never materialised.  The two convolution kernels of frontend.hip run three times per block: forward with
-// the relu(acc + bias) epilogue, and as the data gradient (weights read transposed, taps flipped, plain epilogue).
+// adaptive max pool with its backward (the pool's forward kernel is frontend.h's, here with indices).  fp32 NCHW; the
+// convolution's input is the forward's (x0 nearest-resized, concatenated with an optional x1) and is never materialised.  The two
+// convolution kernels of frontend.hip run three times per block: forward with the relu(acc + bias) epilogue, and as the data
+// gradient (weights read transposed, taps flipped, plain epilogue).
 //
 // Every reduction has a fixed order and no chain is longer than 256 terms:
 //   BatchNorm statistics   a channel's batch * side^2 values are cut into chunks of 256 * T (T = 32; 128 above 2^29 values); a lane
@@ -20,10 +21,14 @@
 
 namespace eg {
 
-constexpr int FB_THREADS = 256;
-
 __host__ __device__ inline int fb_terms(long long n) { return n <= (1ll << 29) ? 32 : 128; }
-inline int fb_chunks(long long n) { return (int)((n + (long long)FB_THREADS * fb_terms(n) - 1) / ((long long)FB_THREADS * fb_terms(n))); }
+inline int fb_chunks(long long n) { return (int)((n + (long long)FE_THREADS * fb_terms(n) - 1) / ((long long)FE_THREADS * fb_terms(n))); }
+// the number of values in chunk `chunk` of a channel's n, T per lane: 256 T but for the last.  The chunk statistics and their
+// combination must agree on it (M2 = sum M2_i + n_i (mean_i - mean)^2)
+__device__ inline float fb_chunk_count(long long chunk, long long n, int T) {
+    const long long left = n - chunk * FE_THREADS * T;
+    return (float)(left < (long long)FE_THREADS * T ? left : (long long)FE_THREADS * T);
+}
 
 // the 256 lanes' values added in a fixed tree; every lane gets the sum
 __device__ inline float fb_block_sum(float v, float* s) {
@@ -32,7 +37,7 @@ __device__ inline float fb_block_sum(float v, float* s) {
     s[t] = v;
     __syncthreads();
 #pragma unroll
-    for (int w = FB_THREADS / 2; w > 0; w >>= 1) {
+    for (int w = FE_THREADS / 2; w > 0; w >>= 1) {
         if (t < w) s[t] += s[t + w];
         __syncthreads();
     }
@@ -49,23 +54,22 @@ __device__ inline size_t fb_at(long long e, int c, int C, int plane) {
 // BatchNorm forward
 // ---------------------------------------------------------------------------
 // grid (chunks, C): part[c][chunk] = (sum, sum of squared deviations from the chunk's mean)
-__global__ __launch_bounds__(FB_THREADS) void k_bn_chunk_stats(const float* __restrict__ r, int C, int plane, long long n, int T,
+__global__ __launch_bounds__(FE_THREADS) void k_bn_chunk_stats(const float* __restrict__ r, int C, int plane, long long n, int T,
                                                                float2* __restrict__ part) {
-    __shared__ float s[FB_THREADS];
+    __shared__ float s[FE_THREADS];
     const int c = blockIdx.y, t = threadIdx.x;
-    const long long base = (long long)blockIdx.x * FB_THREADS * T;
-    const long long left = n - base;
-    const float cnt = (float)(left < (long long)FB_THREADS * T ? left : (long long)FB_THREADS * T);
+    const long long base = (long long)blockIdx.x * FE_THREADS * T;
+    const float cnt = fb_chunk_count(blockIdx.x, n, T);
     float sum = 0.f;
     for (int j = 0; j < T; ++j) {
-        const long long e = base + (long long)j * FB_THREADS + t;
+        const long long e = base + (long long)j * FE_THREADS + t;
         if (e < n) sum += r[fb_at(e, c, C, plane)];
     }
     const float total = fb_block_sum(sum, s);
     const float m = total / cnt;
     float sq = 0.f;
     for (int j = 0; j < T; ++j) {
-        const long long e = base + (long long)j * FB_THREADS + t;
+        const long long e = base + (long long)j * FE_THREADS + t;
         if (e < n) {
             const float d = r[fb_at(e, c, C, plane)] - m;
             sq = fmaf(d, d, sq);
@@ -79,7 +83,7 @@ __global__ __launch_bounds__(FB_THREADS) void k_bn_chunk_stats(const float* __re
 __device__ inline void fb_channel_stats(const float2* __restrict__ part, int c, int chunks, long long n, int T, float* s, float& mean,
                                         float& var) {
     const int t = threadIdx.x;
-    const int per = (chunks + FB_THREADS - 1) / FB_THREADS;             // <= 256: chunks <= 65536
+    const int per = (chunks + FE_THREADS - 1) / FE_THREADS;             // <= 256: chunks <= 65536
     const float2* p = part + (size_t)c * chunks;
     float sum = 0.f;
     for (int j = 0; j < per; ++j) {
@@ -91,8 +95,7 @@ __device__ inline void fb_channel_stats(const float2* __restrict__ part, int c, 
     for (int j = 0; j < per; ++j) {
         const int i = t * per + j;
         if (i < chunks) {
-            const long long left = n - (long long)i * FB_THREADS * T;
-            const float cnt = (float)(left < (long long)FB_THREADS * T ? left : (long long)FB_THREADS * T);
+            const float cnt = fb_chunk_count(i, n, T);
             const float d = p[i].x / cnt - mean;
             m2 += fmaf(cnt * d, d, p[i].y);
         }
@@ -116,17 +119,17 @@ struct FbFwd {
 };
 
 // grid (chunks, C): y = (r - mean) * gamma * invstd + beta; the first chunk's workgroup writes the statistics
-__global__ __launch_bounds__(FB_THREADS) void k_bn_train_apply(const FbFwd A) {
-    __shared__ float s[FB_THREADS];
+__global__ __launch_bounds__(FE_THREADS) void k_bn_train_apply(const FbFwd A) {
+    __shared__ float s[FE_THREADS];
     const int c = blockIdx.y, t = threadIdx.x;
     float mean, var;
     fb_channel_stats(A.part, c, gridDim.x, A.n, A.T, s, mean, var);
     const float invstd = 1.f / sqrtf(var + A.eps);
     const float k = (A.gamma ? A.gamma[c] : 1.f) * invstd;
     const float beta = A.beta ? A.beta[c] : 0.f;
-    const long long base = (long long)blockIdx.x * FB_THREADS * A.T;
+    const long long base = (long long)blockIdx.x * FE_THREADS * A.T;
     for (int j = 0; j < A.T; ++j) {
-        const long long e = base + (long long)j * FB_THREADS + t;
+        const long long e = base + (long long)j * FE_THREADS + t;
         if (e < A.n) {
             const size_t at = fb_at(e, c, A.C, A.plane);
             A.y[at] = (A.r[at] - mean) * k + beta;
@@ -145,17 +148,17 @@ __global__ __launch_bounds__(FB_THREADS) void k_bn_train_apply(const FbFwd A) {
 // ReLU + BatchNorm backward
 // ---------------------------------------------------------------------------
 // grid (chunks, C): part[c][chunk] = (sum dy, sum dy * xhat)
-__global__ __launch_bounds__(FB_THREADS) void k_bn_bwd_chunk_sums(const float* __restrict__ dy, const float* __restrict__ r,
+__global__ __launch_bounds__(FE_THREADS) void k_bn_bwd_chunk_sums(const float* __restrict__ dy, const float* __restrict__ r,
                                                                   const float* __restrict__ save_mean,
                                                                   const float* __restrict__ save_invstd, int C, int plane, long long n,
                                                                   int T, float2* __restrict__ part) {
-    __shared__ float s[FB_THREADS];
+    __shared__ float s[FE_THREADS];
     const int c = blockIdx.y, t = threadIdx.x;
     const float mean = save_mean[c], invstd = save_invstd[c];
-    const long long base = (long long)blockIdx.x * FB_THREADS * T;
+    const long long base = (long long)blockIdx.x * FE_THREADS * T;
     float a = 0.f, b = 0.f;
     for (int j = 0; j < T; ++j) {
-        const long long e = base + (long long)j * FB_THREADS + t;
+        const long long e = base + (long long)j * FE_THREADS + t;
         if (e < n) {
             const size_t at = fb_at(e, c, C, plane);
             const float g = dy[at];
@@ -184,10 +187,10 @@ struct FbBwd {
 };
 
 // grid (chunks, C): dr = gamma invstd (dy - dbeta / n - xhat dgamma / n), dz = dr [r > 0]
-__global__ __launch_bounds__(FB_THREADS) void k_bn_bwd_apply(const FbBwd A) {
-    __shared__ float s[FB_THREADS];
+__global__ __launch_bounds__(FE_THREADS) void k_bn_bwd_apply(const FbBwd A) {
+    __shared__ float s[FE_THREADS];
     const int c = blockIdx.y, t = threadIdx.x, chunks = gridDim.x;
-    const int per = (chunks + FB_THREADS - 1) / FB_THREADS;
+    const int per = (chunks + FE_THREADS - 1) / FE_THREADS;
     const float2* p = A.part + (size_t)c * chunks;
     float a = 0.f, b = 0.f;
     for (int j = 0; j < per; ++j) {
@@ -199,10 +202,10 @@ __global__ __launch_bounds__(FB_THREADS) void k_bn_bwd_apply(const FbBwd A) {
     const float mean = A.save_mean[c], invstd = A.save_invstd[c];
     const float k = (A.gamma ? A.gamma[c] : 1.f) * invstd;
     const float mb = dbeta / (float)A.n, mg = dgamma / (float)A.n;
-    const long long base = (long long)blockIdx.x * FB_THREADS * A.T;
+    const long long base = (long long)blockIdx.x * FE_THREADS * A.T;
     float sum = 0.f;
     for (int j = 0; j < A.T; ++j) {
-        const long long e = base + (long long)j * FB_THREADS + t;
+        const long long e = base + (long long)j * FE_THREADS + t;
         if (e < A.n) {
             const size_t at = fb_at(e, c, A.C, A.plane);
             const float rv = A.r[at];
@@ -228,7 +231,7 @@ __global__ __launch_bounds__(FB_THREADS) void k_bn_bwd_apply(const FbBwd A) {
 // ---------------------------------------------------------------------------
 constexpr int FS_OUT = 32, FS_GROUPS = 8;
 
-__global__ __launch_bounds__(FB_THREADS) void k_sum_slices(const float* __restrict__ part, long long S, int Q, float* __restrict__ out) {
+__global__ __launch_bounds__(FE_THREADS) void k_sum_slices(const float* __restrict__ part, long long S, int Q, float* __restrict__ out) {
     __shared__ float s[FS_GROUPS][FS_OUT];
     const int ql = threadIdx.x % FS_OUT, g = threadIdx.x / FS_OUT;
     const int q = blockIdx.x * FS_OUT + ql;
@@ -254,7 +257,7 @@ __global__ __launch_bounds__(FB_THREADS) void k_sum_slices(const float* __restri
 }
 
 static void fs_launch(const float* part, long long S, int Q, float* out, hipStream_t stream) {
-    hipLaunchKernelGGL(k_sum_slices, dim3((unsigned)((Q + FS_OUT - 1) / FS_OUT)), dim3(FB_THREADS), 0, stream, part, S, Q, out);
+    hipLaunchKernelGGL(k_sum_slices, dim3((unsigned)((Q + FS_OUT - 1) / FS_OUT)), dim3(FE_THREADS), 0, stream, part, S, Q, out);
 }
 
 // ---------------------------------------------------------------------------
@@ -262,9 +265,9 @@ static void fs_launch(const float* part, long long S, int Q, float* out, hipStre
 // ---------------------------------------------------------------------------
 constexpr int FR_MAX_RATIO = 16;
 
-__global__ __launch_bounds__(FB_THREADS) void k_resize_bwd(const float* __restrict__ full, long long total, int side0, int side,
+__global__ __launch_bounds__(FE_THREADS) void k_resize_bwd(const float* __restrict__ full, long long total, int side0, int side,
                                                            float* __restrict__ dx0) {
-    const long long e = (long long)blockIdx.x * FB_THREADS + threadIdx.x;
+    const long long e = (long long)blockIdx.x * FE_THREADS + threadIdx.x;
     if (e >= total) return;
     const int plane0 = side0 * side0;
     const long long pl = e / plane0;
@@ -301,8 +304,8 @@ struct FwArgs {
 
 // OB x CB (output, input) channel pairs, 256 / (OB CB) pixel slices per pair
 template <int OB, int CB>
-__global__ __launch_bounds__(FB_THREADS) void k_conv3x3_wgrad(const FwArgs A) {
-    constexpr int PS = FB_THREADS / (OB * CB);
+__global__ __launch_bounds__(FE_THREADS) void k_conv3x3_wgrad(const FwArgs A) {
+    constexpr int PS = FE_THREADS / (OB * CB);
     __shared__ float s_x[CB][FW_XS];
     __shared__ float s_dz[OB][FW_DS];
     __shared__ int s_base[FW_PX];
@@ -318,7 +321,7 @@ __global__ __launch_bounds__(FB_THREADS) void k_conv3x3_wgrad(const FwArgs A) {
     const int o0 = blockIdx.y * OB, cb0 = blockIdx.z * CB;
     const int npix = A.frames * tw * th, npos = A.frames * lw * lh;       // <= FW_PX, <= FW_POS (the launcher's choice of frames)
 
-    for (int pos = t; pos < npos; pos += FB_THREADS) {
+    for (int pos = t; pos < npos; pos += FE_THREADS) {
         const int f = pos / (lw * lh), q = pos - f * (lw * lh);
         const int ly = q / lw, lx = q - ly * lw;
         const int b = b0 + f, y = y_lo + ly - 1, x = x_lo + lx - 1;
@@ -416,38 +419,13 @@ static size_t ws_wgrad_bytes(int batch, int c_in, int c_out, int side) {
 }
 
 // ---------------------------------------------------------------------------
-// adaptive max pool with indices, and its backward in gather form
+// the adaptive max pool's backward in gather form (the forward is frontend.h's k_adaptive_max_pool<true>)
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(FB_THREADS) void k_adaptive_max_pool_idx(const float* __restrict__ x, long long total, int side_in,
-                                                                      int side_out, float* __restrict__ out, int* __restrict__ idx) {
-    const long long e = (long long)blockIdx.x * FB_THREADS + threadIdx.x;
-    if (e >= total) return;
-    const int plane_out = side_out * side_out;
-    const long long pl = e / plane_out;
-    const int r = (int)(e - pl * plane_out);
-    const int i = r / side_out, j = r - i * side_out;
-    const int y0 = (i * side_in) / side_out, y1 = ((i + 1) * side_in + side_out - 1) / side_out;
-    const int x0 = (j * side_in) / side_out, x1 = ((j + 1) * side_in + side_out - 1) / side_out;
-    const float* src = x + pl * side_in * side_in;
-    float m = -INFINITY;
-    int at = y0 * side_in + x0;
-    for (int yy = y0; yy < y1; ++yy)
-        for (int xx = x0; xx < x1; ++xx) {
-            const float v = src[yy * side_in + xx];
-            if (v > m || v != v) {                       // torch's rule: the first maximum in scan order; a NaN always takes over
-                m = v;
-                at = yy * side_in + xx;
-            }
-        }
-    out[e] = m;
-    idx[e] = at;
-}
-
 // one lane per INPUT pixel: the windows that contain it, in row-major order, give their dy where it is their maximum
-__global__ __launch_bounds__(FB_THREADS) void k_adaptive_max_pool_bwd(const float* __restrict__ dy, const int* __restrict__ idx,
+__global__ __launch_bounds__(FE_THREADS) void k_adaptive_max_pool_bwd(const float* __restrict__ dy, const int* __restrict__ idx,
                                                                       long long total, int side_in, int side_out,
                                                                       float* __restrict__ dx) {
-    const long long e = (long long)blockIdx.x * FB_THREADS + threadIdx.x;
+    const long long e = (long long)blockIdx.x * FE_THREADS + threadIdx.x;
     if (e >= total) return;
     const int plane_in = side_in * side_in, plane_out = side_out * side_out;
     const long long pl = e / plane_in;
@@ -465,17 +443,6 @@ __global__ __launch_bounds__(FB_THREADS) void k_adaptive_max_pool_bwd(const floa
         for (int j = j_lo; j < j_hi; ++j)
             if (ix[i * side_out + j] == q) sum += g[i * side_out + j];
     dx[e] = sum;
-}
-
-static int pool_check(const void* a, const void* b, int planes, int side_in, int side_out) {
-    if (!a || !b) return set_error(EG_ERR_ARG, "a required pointer is NULL");
-    if (planes < 1) return set_error(EG_ERR_ARG, "planes must be >= 1");
-    if (side_out < 1 || side_in < 1) return set_error(EG_ERR_ARG, "side_in and side_out must be >= 1");
-    if (side_out > side_in) return set_error(EG_ERR_ARG, "side_out must not exceed side_in");
-    if (side_in > FE_MAX_SIDE) return set_error(EG_ERR_UNSUPPORTED, "sides above 512 are not covered");
-    if (((long long)planes * side_in * side_in + FB_THREADS - 1) / FB_THREADS >= (1ll << 31))
-        return set_error(EG_ERR_UNSUPPORTED, "planes * side_in^2 too large for one launch");
-    return EG_OK;
 }
 
 static int bn_check(int batch, int channels, int side) {
@@ -501,10 +468,12 @@ size_t eg_frontend_train_workspace_bytes(int batch, int c_in, int c_out, int sid
 int eg_conv3x3_relu_fwd(const float* x0, int c0, int side0, const float* x1, int c1, int batch, int side, const float* weight,
                         const float* bias, int c_out, float* r, eg_stream_t stream) {
     if (!x0 || !weight || !r) return set_error(EG_ERR_ARG, "x0, weight and r must not be NULL");
-    if ((c1 > 0) != (x1 != nullptr)) return set_error(EG_ERR_ARG, "x1 must be given exactly when c1 > 0");
+    if (const int rc = fe_check_x1(x1, c1)) return rc;
     if (r == x0 || r == x1) return set_error(EG_ERR_ARG, "r must not alias an input");
     if (const int rc = fe_check_shapes(batch, c0, c1, c_out, side, side0)) return rc;
-    FeConv A{x0, x1, weight, bias, nullptr, nullptr, nullptr, nullptr, r, 0.f, c0, c1, c_out, batch, side, side0, nullptr, 0};
+    FeConv A;
+    A.x0 = x0; A.x1 = x1; A.weight = weight; A.bias = bias; A.out = r;
+    A.c0 = c0; A.c1 = c1; A.c_out = c_out; A.batch = batch; A.side = side; A.side0 = side0;
     return fe_launch_conv(A, FE_RELU, (hipStream_t)stream);
 }
 
@@ -521,9 +490,9 @@ int eg_bn2d_train_fwd(const float* r, int batch, int channels, int side, const f
     const int T = fb_terms(n), chunks = fb_chunks(n);
     float2* part = (float2*)workspace;
     const dim3 grid((unsigned)chunks, (unsigned)channels);
-    hipLaunchKernelGGL(k_bn_chunk_stats, grid, dim3(FB_THREADS), 0, (hipStream_t)stream, r, channels, side * side, n, T, part);
+    hipLaunchKernelGGL(k_bn_chunk_stats, grid, dim3(FE_THREADS), 0, (hipStream_t)stream, r, channels, side * side, n, T, part);
     FbFwd A{r, part, gamma, beta, running_mean, running_var, y, save_mean, save_invstd, n, eps, momentum, channels, side * side, T};
-    hipLaunchKernelGGL(k_bn_train_apply, grid, dim3(FB_THREADS), 0, (hipStream_t)stream, A);
+    hipLaunchKernelGGL(k_bn_train_apply, grid, dim3(FE_THREADS), 0, (hipStream_t)stream, A);
     EG_HIP_TRY(hipGetLastError());
     return EG_OK;
 }
@@ -540,10 +509,10 @@ int eg_relu_bn2d_bwd(const float* dy, const float* r, const float* save_mean, co
     float2* part = (float2*)workspace;
     float* dz_part = (float*)((char*)workspace + ws_bn_bytes(batch, channels, side));
     const dim3 grid((unsigned)chunks, (unsigned)channels);
-    hipLaunchKernelGGL(k_bn_bwd_chunk_sums, grid, dim3(FB_THREADS), 0, (hipStream_t)stream, dy, r, save_mean, save_invstd, channels,
+    hipLaunchKernelGGL(k_bn_bwd_chunk_sums, grid, dim3(FE_THREADS), 0, (hipStream_t)stream, dy, r, save_mean, save_invstd, channels,
                        side * side, n, T, part);
     FbBwd A{dy, r, save_mean, save_invstd, gamma, part, dz, dz_part, dgamma, dbeta, n, channels, side * side, T};
-    hipLaunchKernelGGL(k_bn_bwd_apply, grid, dim3(FB_THREADS), 0, (hipStream_t)stream, A);
+    hipLaunchKernelGGL(k_bn_bwd_apply, grid, dim3(FE_THREADS), 0, (hipStream_t)stream, A);
     if (dbias) fs_launch(dz_part, chunks, channels, dbias, (hipStream_t)stream);
     EG_HIP_TRY(hipGetLastError());
     return EG_OK;
@@ -560,13 +529,14 @@ int eg_conv3x3_bwd_data(const float* dz, const float* weight, int batch, int c_o
     if (dx0 && resized && (side + side0 - 1) / side0 > FR_MAX_RATIO)
         return set_error(EG_ERR_UNSUPPORTED, "enlargements above 16 x are not covered by the backward");
     // the forward kernels on dz: c_out input channels, c0 + c1 output channels, split at c0
-    FeConv A{dz, nullptr, weight, nullptr, nullptr, nullptr, nullptr, nullptr, dx0 ? (resized ? full : dx0) : nullptr, 0.f,
-             c_out, 0, c0 + c1, batch, side, side, dx1, c0};
+    FeConv A;
+    A.x0 = dz; A.weight = weight; A.out = dx0 ? (resized ? full : dx0) : nullptr; A.out1 = dx1; A.split = c0;
+    A.c0 = c_out; A.c_out = c0 + c1; A.batch = batch; A.side = A.side0 = side;
     if (const int rc = fe_launch_conv(A, FE_DGRAD, (hipStream_t)stream)) return rc;
     if (dx0 && resized) {
         const long long total = (long long)batch * c0 * side0 * side0;
-        hipLaunchKernelGGL(k_resize_bwd, dim3((unsigned)((total + FB_THREADS - 1) / FB_THREADS)), dim3(FB_THREADS), 0,
-                           (hipStream_t)stream, full, total, side0, side, dx0);
+        hipLaunchKernelGGL(k_resize_bwd, dim3((unsigned)fe_blocks(total)), dim3(FE_THREADS), 0, (hipStream_t)stream, full, total, side0,
+                           side, dx0);
         EG_HIP_TRY(hipGetLastError());
     }
     return EG_OK;
@@ -575,7 +545,7 @@ int eg_conv3x3_bwd_data(const float* dz, const float* weight, int batch, int c_o
 int eg_conv3x3_bwd_weight(const float* x0, int c0, int side0, const float* x1, int c1, int batch, int side, const float* dz, int c_out,
                           void* workspace, float* dweight, eg_stream_t stream) {
     if (!x0 || !dz || !dweight) return set_error(EG_ERR_ARG, "x0, dz and dweight must not be NULL");
-    if ((c1 > 0) != (x1 != nullptr)) return set_error(EG_ERR_ARG, "x1 must be given exactly when c1 > 0");
+    if (const int rc = fe_check_x1(x1, c1)) return rc;
     if (const int rc = fe_check_shapes(batch, c0, c1, c_out, side, side0)) return rc;
     const int c_in = c0 + c1;
     const FwTiling g = fw_tiling(batch, side);
@@ -583,10 +553,10 @@ int eg_conv3x3_bwd_weight(const float* x0, int c0, int side0, const float* x1, i
     float* part = g.slices > 1 ? (float*)((char*)workspace + ws_bn_bytes(batch, c_out, side) + ws_dz_bytes(batch, c_out, side)) : dweight;
     FwArgs A{x0, x1, dz, part, c0, c1, c_out, batch, side, side0, g.tw, g.th, g.tiles_x, g.tiles_per_frame, g.frames};
     if (c_in <= 8 && c_out <= 8)
-        hipLaunchKernelGGL((k_conv3x3_wgrad<8, 8>), dim3((unsigned)g.slices, (c_out + 7) / 8, (c_in + 7) / 8), dim3(FB_THREADS), 0,
+        hipLaunchKernelGGL((k_conv3x3_wgrad<8, 8>), dim3((unsigned)g.slices, (c_out + 7) / 8, (c_in + 7) / 8), dim3(FE_THREADS), 0,
                            (hipStream_t)stream, A);
     else
-        hipLaunchKernelGGL((k_conv3x3_wgrad<16, 16>), dim3((unsigned)g.slices, (c_out + 15) / 16, (c_in + 15) / 16), dim3(FB_THREADS),
+        hipLaunchKernelGGL((k_conv3x3_wgrad<16, 16>), dim3((unsigned)g.slices, (c_out + 15) / 16, (c_in + 15) / 16), dim3(FE_THREADS),
                            0, (hipStream_t)stream, A);
     if (g.slices > 1) fs_launch(part, g.slices, c_out * c_in * 9, dweight, (hipStream_t)stream);
     EG_HIP_TRY(hipGetLastError());
@@ -594,23 +564,21 @@ int eg_conv3x3_bwd_weight(const float* x0, int c0, int side0, const float* x1, i
 }
 
 int eg_adaptive_max_pool_idx_fwd(const float* x, int planes, int side_in, int side_out, float* out, int* idx, eg_stream_t stream) {
-    if (const int rc = pool_check(x, out, planes, side_in, side_out)) return rc;
+    if (const int rc = fe_pool_check(x, out, "a required pointer is NULL", planes, side_in, side_out)) return rc;
+    if (fe_pool_too_large(planes, side_in)) return set_error(EG_ERR_UNSUPPORTED, "planes * side_in^2 too large for one launch");
     if (!idx) return set_error(EG_ERR_ARG, "idx must not be NULL");
     if (out == x) return set_error(EG_ERR_ARG, "out must not alias x");
-    const long long total = (long long)planes * side_out * side_out;
-    hipLaunchKernelGGL(k_adaptive_max_pool_idx, dim3((unsigned)((total + FB_THREADS - 1) / FB_THREADS)), dim3(FB_THREADS), 0,
-                       (hipStream_t)stream, x, total, side_in, side_out, out, idx);
-    EG_HIP_TRY(hipGetLastError());
-    return EG_OK;
+    return fe_pool_forward<true>(x, planes, side_in, side_out, out, idx, (hipStream_t)stream);
 }
 
 int eg_adaptive_max_pool_bwd(const float* dy, const int* idx, int planes, int side_in, int side_out, float* dx, eg_stream_t stream) {
-    if (const int rc = pool_check(dy, dx, planes, side_in, side_out)) return rc;
+    if (const int rc = fe_pool_check(dy, dx, "a required pointer is NULL", planes, side_in, side_out)) return rc;
+    if (fe_pool_too_large(planes, side_in)) return set_error(EG_ERR_UNSUPPORTED, "planes * side_in^2 too large for one launch");
     if (!idx) return set_error(EG_ERR_ARG, "idx must not be NULL");
     if (dx == dy) return set_error(EG_ERR_ARG, "dx must not alias dy");
     const long long total = (long long)planes * side_in * side_in;
-    hipLaunchKernelGGL(k_adaptive_max_pool_bwd, dim3((unsigned)((total + FB_THREADS - 1) / FB_THREADS)), dim3(FB_THREADS), 0,
-                       (hipStream_t)stream, dy, idx, total, side_in, side_out, dx);
+    hipLaunchKernelGGL(k_adaptive_max_pool_bwd, dim3((unsigned)fe_blocks(total)), dim3(FE_THREADS), 0, (hipStream_t)stream, dy, idx,
+                       total, side_in, side_out, dx);
     EG_HIP_TRY(hipGetLastError());
     return EG_OK;
 }

@@ -60,7 +60,7 @@ def _check_block(block, where: str, training: bool = False) -> None:
         _check_bn(getattr(block, bn), f"{where}.{bn}", training)
 
 
-def _structure(down_convs, up_convs, frames, training: bool = False):
+def _structure(down_convs, up_convs, frames, training: bool):
     """The structure checks both routes share -> (down blocks, up blocks, pool sides, upsample sides)."""
     down_convs, up_convs = list(down_convs), list(up_convs)
     if len(down_convs) != len(up_convs):
@@ -82,6 +82,26 @@ def _structure(down_convs, up_convs, frames, training: bool = False):
     return down_convs, up_convs, pools, sizes
 
 
+def _walk(down_convs, up_convs, frames, conv, pool, training: bool) -> List[torch.Tensor]:
+    """The walk over the blocks both routes make, on the convolution and pool operators of one mode."""
+    down_convs, up_convs, pools, sizes = _structure(down_convs, up_convs, frames, training)
+    x, skips = frames.contiguous(), []
+    for down, side_out in zip(down_convs, pools):
+        skips.append(x)
+        x = conv(x, down.conv1.weight, down.conv1.bias, down.BN1)
+        x = conv(x, down.conv2.weight, down.conv2.bias, down.BN2)
+        x = pool(x, side_out)
+    feats = [x]
+    for up, side in zip(up_convs, sizes):
+        skip = skips.pop()
+        if skip.shape[2] != side:
+            _refuse("up_convs", f"upsample.size {side} does not meet the skip map's side {skip.shape[2]}")
+        x = conv(x, up.conv1.weight, up.conv1.bias, up.BN1, side=side)                                  # upsample + conv1
+        x = conv(x, up.conv2.weight, up.conv2.bias, up.BN2, x1=skip)                                    # cat([x, skip]) + conv2
+        feats.append(x)
+    return feats
+
+
 def unet_decoder_maps(down_convs, up_convs, frames: torch.Tensor) -> List[torch.Tensor]:
     """The decoder's maps, coarse to fine, of the reference's UNet front-end in eval mode: what
 
@@ -94,22 +114,7 @@ def unet_decoder_maps(down_convs, up_convs, frames: torch.Tensor) -> List[torch.
     7 + 7).  Blocks are anything with the reference's attribute names: down.conv1 / BN1 / conv2 / BN2 / pool.output_size,
     up.upsample.size / conv1 / BN1 / conv2 / BN2.  Parameters and running statistics are read at the call: nothing is cached.
     Inference only; NotImplementedError for a block outside this structure."""
-    down_convs, up_convs, pools, sizes = _structure(down_convs, up_convs, frames)
-    x, skips = frames.contiguous(), []
-    for down, side_out in zip(down_convs, pools):
-        skips.append(x)
-        x = F_ops.conv3x3_relu_bn(x, down.conv1.weight, down.conv1.bias, down.BN1)
-        x = F_ops.conv3x3_relu_bn(x, down.conv2.weight, down.conv2.bias, down.BN2)
-        x = F_ops.adaptive_max_pool(x, side_out)
-    feats = [x]
-    for up, side in zip(up_convs, sizes):
-        skip = skips.pop()
-        if skip.shape[2] != side:
-            _refuse("up_convs", f"upsample.size {side} does not meet the skip map's side {skip.shape[2]}")
-        x = F_ops.conv3x3_relu_bn(x, up.conv1.weight, up.conv1.bias, up.BN1, side=side)                 # upsample + conv1
-        x = F_ops.conv3x3_relu_bn(x, up.conv2.weight, up.conv2.bias, up.BN2, x1=skip)                   # cat([x, skip]) + conv2
-        feats.append(x)
-    return feats
+    return _walk(down_convs, up_convs, frames, F_ops.conv3x3_relu_bn, F_ops.adaptive_max_pool, training=False)
 
 
 def unet_decoder_maps_train(down_convs, up_convs, frames: torch.Tensor) -> List[torch.Tensor]:
@@ -118,19 +123,4 @@ def unet_decoder_maps_train(down_convs, up_convs, frames: torch.Tensor) -> List[
     ops.adaptive_max_pool_train.  Skips, the upsample and the concatenation are passed as sources, as in eval: autograd saves the
     ReLU outputs, the batch statistics and the pools' indices, never an upsampled or concatenated map.  91 launches forward for
     the default 7 + 7; bit-reproducible; capturable.  NotImplementedError for a block outside the structure."""
-    down_convs, up_convs, pools, sizes = _structure(down_convs, up_convs, frames, training=True)
-    x, skips = frames.contiguous(), []
-    for down, side_out in zip(down_convs, pools):
-        skips.append(x)
-        x = F_ops.conv3x3_relu_bn_train(x, down.conv1.weight, down.conv1.bias, down.BN1)
-        x = F_ops.conv3x3_relu_bn_train(x, down.conv2.weight, down.conv2.bias, down.BN2)
-        x = F_ops.adaptive_max_pool_train(x, side_out)
-    feats = [x]
-    for up, side in zip(up_convs, sizes):
-        skip = skips.pop()
-        if skip.shape[2] != side:
-            _refuse("up_convs", f"upsample.size {side} does not meet the skip map's side {skip.shape[2]}")
-        x = F_ops.conv3x3_relu_bn_train(x, up.conv1.weight, up.conv1.bias, up.BN1, side=side)           # upsample + conv1
-        x = F_ops.conv3x3_relu_bn_train(x, up.conv2.weight, up.conv2.bias, up.BN2, x1=skip)             # cat([x, skip]) + conv2
-        feats.append(x)
-    return feats
+    return _walk(down_convs, up_convs, frames, F_ops.conv3x3_relu_bn_train, F_ops.adaptive_max_pool_train, training=True)

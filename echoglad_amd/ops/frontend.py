@@ -1,7 +1,7 @@
 """The UNet front-end's operators: conv3x3 -> ReLU -> BatchNorm, whose input may be a nearest-resized map concatenated with a second
-one, and the adaptive max pool.  `conv3x3_relu_bn` / `adaptive_max_pool` (frontend.hip) are the eval-mode forward, one launch each,
-inference only; `conv3x3_relu_bn_train` / `adaptive_max_pool_train` (frontend_train.hip) are the training-mode block with batch
-statistics and the pool, each with a backward."""
+one, and the adaptive max pool.  `conv3x3_relu_bn` / `adaptive_max_pool` are the eval-mode forward, one launch each, inference only;
+`conv3x3_relu_bn_train` / `adaptive_max_pool_train` are the training-mode block with batch statistics and the pool, each with a
+backward.  Both modes check their arguments with the same helpers (`_conv_args`, `_bn_parts`, `_on_device`, `_pool_args`)."""
 from __future__ import annotations
 
 from typing import Optional
@@ -13,6 +13,7 @@ from ._core import _check, _on_current_device, _scratch, call, raw
 
 MAX_SIDE = 512
 MAX_CHANNELS = 512
+MAX_ENLARGEMENT = 16        # training mode: the resize backward adds a source pixel's destination block in one chain: <= 16 x 16 terms
 
 
 def _no_grad_needed(what: str, *tensors) -> None:
@@ -30,33 +31,8 @@ def _square_map(t: torch.Tensor, name: str) -> None:
         raise RuntimeError(f"{name} must be a contiguous float32 tensor, got {t.dtype}, contiguous = {t.is_contiguous()}")
 
 
-def _bn_parts(bn, c_out: int):
-    """(weight, bias, running_mean, running_var, eps) of an nn.BatchNorm2d in eval mode, or of a 5-tuple as it is."""
-    if isinstance(bn, torch.nn.modules.batchnorm._BatchNorm):
-        if bn.running_mean is None or bn.running_var is None:
-            raise RuntimeError("bn has no running statistics (track_running_stats=False): the eval-mode front-end needs them")
-        if bn.training:
-            raise RuntimeError("bn is in training mode (batch statistics): conv3x3_relu_bn is inference-only")
-        parts = (bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
-    else:
-        parts = tuple(bn)
-        if len(parts) != 5:
-            raise RuntimeError("bn must be an nn.BatchNorm2d or a 5-tuple (weight, bias, running_mean, running_var, eps)")
-    gamma, beta, mean, var, eps = parts
-    if mean is None or var is None:
-        raise RuntimeError("bn needs running_mean and running_var")
-    for t, name in ((gamma, "bn weight"), (beta, "bn bias"), (mean, "bn running_mean"), (var, "bn running_var")):
-        if t is not None and (t.dtype != torch.float32 or t.numel() != c_out):
-            raise RuntimeError(f"{name} must be float32 with {c_out} elements, got {tuple(t.shape)} {t.dtype}")
-    return gamma, beta, mean, var, float(eps)
-
-
-def conv3x3_relu_bn(x0: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], bn, side: Optional[int] = None,
-                    x1: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """BatchNorm_eval(relu(conv3x3(cat([nearest_resize(x0, side), x1], dim=1)) + bias)) -> [batch, c_out, side, side]
-    (eg_conv3x3_relu_bn_fwd; zero padding 1).  x0 [batch, c0, side0, side0]; side None: side0 (no resize); x1 [batch, c1, side,
-    side] or None; weight [c_out, c0 + c1, 3, 3] as nn.Conv2d holds it; bias [c_out] or None; bn an nn.BatchNorm2d in eval mode
-    or (weight, bias, running_mean, running_var, eps) with weight / bias possibly None.  Parameters are read at the call."""
+def _conv_args(x0, weight, bias, side, x1):
+    """The shape, dtype and limit checks both convolution operators make -> (batch, c0, side0, side, c1, c_out)."""
     _square_map(x0, "x0")
     batch, c0, side0 = int(x0.shape[0]), int(x0.shape[1]), int(x0.shape[2])
     side = side0 if side is None else int(side)
@@ -78,14 +54,78 @@ def conv3x3_relu_bn(x0: torch.Tensor, weight: torch.Tensor, bias: Optional[torch
                            f"sides {side0} -> {side}, channels {c0} + {c1} -> {c_out}")
     if bias is not None and (bias.dtype != torch.float32 or bias.numel() != c_out):
         raise RuntimeError(f"bias must be float32 with {c_out} elements, got {tuple(bias.shape)} {bias.dtype}")
-    gamma, beta, mean, var, eps = _bn_parts(bn, c_out)
-    _no_grad_needed("conv3x3_relu_bn", x0, x1, weight, bias, gamma, beta)
-    _check(x0, "x0")
-    _on_current_device(x0, "x0")
-    for t, name in ((x1, "x1"), (weight, "weight"), (bias, "bias"), (gamma, "bn weight"), (beta, "bn bias"),
-                    (mean, "bn running_mean"), (var, "bn running_var")):
+    return batch, c0, side0, side, c1, c_out
+
+
+def _bn_parts(bn, c_out: int, training: bool):
+    """(weight, bias, running_mean, running_var, eps, momentum, module or None) of an nn.BatchNorm2d that is in the mode asked for,
+    or of a tuple as it is: 5 entries in eval mode (momentum comes back None), 6 with the momentum in training mode."""
+    module = None
+    if isinstance(bn, torch.nn.modules.batchnorm._BatchNorm):
+        if training:
+            if not bn.training:
+                raise RuntimeError("bn is in eval mode (running statistics): conv3x3_relu_bn_train takes a BatchNorm in training mode; "
+                                   "conv3x3_relu_bn is the eval-mode operator")
+            if not bn.track_running_stats or bn.running_mean is None or bn.running_var is None:
+                raise NotImplementedError("conv3x3_relu_bn_train: a BatchNorm with track_running_stats=False is not covered")
+        else:
+            if bn.running_mean is None or bn.running_var is None:
+                raise RuntimeError("bn has no running statistics (track_running_stats=False): the eval-mode front-end needs them")
+            if bn.training:
+                raise RuntimeError("bn is in training mode (batch statistics): conv3x3_relu_bn is inference-only")
+        parts = (bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps) + ((bn.momentum,) if training else ())
+        module = bn
+    else:
+        parts = tuple(bn)
+        if len(parts) != (6 if training else 5):
+            raise RuntimeError("bn must be an nn.BatchNorm2d or a " + ("6-tuple (weight, bias, running_mean, running_var, eps, momentum)"
+                                                                       if training else "5-tuple (weight, bias, running_mean, running_var, eps)"))
+    if training and parts[5] is None:
+        raise NotImplementedError("conv3x3_relu_bn_train: momentum=None (a cumulative moving average) is not covered")
+    gamma, beta, mean, var, eps = parts[:5]
+    if not training and (mean is None or var is None):
+        raise RuntimeError("bn needs running_mean and running_var")
+    for t, name in ((gamma, "bn weight"), (beta, "bn bias"), (mean, "bn running_mean"), (var, "bn running_var")):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != c_out):
+            raise RuntimeError(f"{name} must be float32 with {c_out} elements, got {tuple(t.shape)} {t.dtype}")
+    return gamma, beta, mean, var, float(eps), float(parts[5]) if training else None, module
+
+
+def _on_device(first, name: str, *others) -> None:
+    """`first` is a tensor of the current device the kernels take; every (tensor, name) after it that is given sits there with it."""
+    _check(first, name)
+    _on_current_device(first, name)
+    for t, other in others:
         if t is not None:
-            _check(t, name, device=x0.device)
+            _check(t, other, device=first.device)
+
+
+def _conv_on_device(x0, x1, weight, bias, gamma, beta, mean, var) -> None:
+    _on_device(x0, "x0", (x1, "x1"), (weight, "weight"), (bias, "bias"), (gamma, "bn weight"), (beta, "bn bias"),
+               (mean, "bn running_mean"), (var, "bn running_var"))
+
+
+def _pool_args(x, side_out) -> int:
+    """The checks both pools make -> side_out."""
+    _square_map(x, "x")
+    side_out, side_in = int(side_out), int(x.shape[2])
+    if not 1 <= side_out <= side_in <= MAX_SIDE:
+        raise RuntimeError(f"side_out must be in 1 .. side_in = {side_in} <= {MAX_SIDE}, got {side_out}")
+    if int(x.shape[0]) * int(x.shape[1]) < 1:
+        raise RuntimeError("x has no planes")
+    return side_out
+
+
+def conv3x3_relu_bn(x0: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], bn, side: Optional[int] = None,
+                    x1: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """BatchNorm_eval(relu(conv3x3(cat([nearest_resize(x0, side), x1], dim=1)) + bias)) -> [batch, c_out, side, side]
+    (eg_conv3x3_relu_bn_fwd; zero padding 1).  x0 [batch, c0, side0, side0]; side None: side0 (no resize); x1 [batch, c1, side,
+    side] or None; weight [c_out, c0 + c1, 3, 3] as nn.Conv2d holds it; bias [c_out] or None; bn an nn.BatchNorm2d in eval mode
+    or (weight, bias, running_mean, running_var, eps) with weight / bias possibly None.  Parameters are read at the call."""
+    batch, c0, side0, side, c1, c_out = _conv_args(x0, weight, bias, side, x1)
+    gamma, beta, mean, var, eps, _, _ = _bn_parts(bn, c_out, training=False)
+    _no_grad_needed("conv3x3_relu_bn", x0, x1, weight, bias, gamma, beta)
+    _conv_on_device(x0, x1, weight, bias, gamma, beta, mean, var)
     out = torch.empty((batch, c_out, side, side), dtype=torch.float32, device=x0.device)
     call("eg_conv3x3_relu_bn_fwd", x0.detach(), c0, side0, None if x1 is None else x1.detach(), c1, batch, side, weight.detach(),
          None if bias is None else bias.detach(), None if gamma is None else gamma.detach(),
@@ -95,55 +135,17 @@ def conv3x3_relu_bn(x0: torch.Tensor, weight: torch.Tensor, bias: Optional[torch
 
 def adaptive_max_pool(x: torch.Tensor, side_out: int) -> torch.Tensor:
     """nn.AdaptiveMaxPool2d(side_out) of a square NCHW map -> [batch, channels, side_out, side_out] (eg_adaptive_max_pool_fwd)."""
-    _square_map(x, "x")
-    side_out = int(side_out)
-    side_in = int(x.shape[2])
-    if not 1 <= side_out <= side_in <= MAX_SIDE:
-        raise RuntimeError(f"side_out must be in 1 .. side_in = {side_in} <= {MAX_SIDE}, got {side_out}")
-    planes = int(x.shape[0]) * int(x.shape[1])
-    if planes < 1:
-        raise RuntimeError("x has no planes")
+    side_out = _pool_args(x, side_out)
     _no_grad_needed("adaptive_max_pool", x)
-    _check(x, "x")
-    _on_current_device(x, "x")
+    _on_device(x, "x")
     out = torch.empty((x.shape[0], x.shape[1], side_out, side_out), dtype=torch.float32, device=x.device)
-    call("eg_adaptive_max_pool_fwd", x.detach(), planes, side_in, side_out, out)
+    call("eg_adaptive_max_pool_fwd", x.detach(), int(x.shape[0]) * int(x.shape[1]), int(x.shape[2]), side_out, out)
     return out
 
 
 # ---------------------------------------------------------------------------
 # training mode
 # ---------------------------------------------------------------------------
-MAX_ENLARGEMENT = 16        # the resize backward adds a source pixel's destination block in one chain: <= 16 x 16 terms
-
-
-def _bn_train_parts(bn, c_out: int):
-    """(weight, bias, running_mean, running_var, eps, momentum, module or None) of an nn.BatchNorm2d in training mode, or of a
-    6-tuple as it is."""
-    module = None
-    if isinstance(bn, torch.nn.modules.batchnorm._BatchNorm):
-        if not bn.training:
-            raise RuntimeError("bn is in eval mode (running statistics): conv3x3_relu_bn_train takes a BatchNorm in training mode; "
-                               "conv3x3_relu_bn is the eval-mode operator")
-        if not bn.track_running_stats or bn.running_mean is None or bn.running_var is None:
-            raise NotImplementedError("conv3x3_relu_bn_train: a BatchNorm with track_running_stats=False is not covered")
-        if bn.momentum is None:
-            raise NotImplementedError("conv3x3_relu_bn_train: momentum=None (a cumulative moving average) is not covered")
-        parts = (bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum)
-        module = bn
-    else:
-        parts = tuple(bn)
-        if len(parts) != 6:
-            raise RuntimeError("bn must be an nn.BatchNorm2d or a 6-tuple (weight, bias, running_mean, running_var, eps, momentum)")
-        if parts[5] is None:
-            raise NotImplementedError("conv3x3_relu_bn_train: momentum=None (a cumulative moving average) is not covered")
-    gamma, beta, mean, var, eps, momentum = parts
-    for t, name in ((gamma, "bn weight"), (beta, "bn bias"), (mean, "bn running_mean"), (var, "bn running_var")):
-        if t is not None and (t.dtype != torch.float32 or t.numel() != c_out):
-            raise RuntimeError(f"{name} must be float32 with {c_out} elements, got {tuple(t.shape)} {t.dtype}")
-    return gamma, beta, mean, var, float(eps), float(momentum), module
-
-
 def _train_workspace(device, batch: int, c_in: int, c_out: int, side: int) -> torch.Tensor:
     """The block's workspace (eg_frontend_train_workspace_bytes): chunk statistics and the weight gradient's slices."""
     return _scratch("frontend_train", device, max(int(raw("eg_frontend_train_workspace_bytes", batch, c_in, c_out, side)), 256))
@@ -210,38 +212,13 @@ def conv3x3_relu_bn_train(x0: torch.Tensor, weight: torch.Tensor, bias: Optional
     arguments are `conv3x3_relu_bn`'s; bn is an nn.BatchNorm2d in TRAINING mode -- its running statistics and
     num_batches_tracked move as nn.BatchNorm2d moves them -- or (weight, bias, running_mean | None, running_var | None, eps,
     momentum).  3 launches forward (eg_conv3x3_relu_fwd, eg_bn2d_train_fwd), up to 7 backward; bit-reproducible, capturable."""
-    _square_map(x0, "x0")
-    batch, c0, side0 = int(x0.shape[0]), int(x0.shape[1]), int(x0.shape[2])
-    side = side0 if side is None else int(side)
-    c1 = 0
-    if x1 is not None:
-        _square_map(x1, "x1")
-        if x1.shape[0] != batch or x1.shape[2] != side:
-            raise RuntimeError(f"x1 must be [{batch}, *, {side}, {side}] next to x0 {tuple(x0.shape)} at side {side}, got {tuple(x1.shape)}")
-        c1 = int(x1.shape[1])
-    if not isinstance(weight, torch.Tensor) or weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
-        raise RuntimeError(f"weight must be [c_out, c_in, 3, 3], got {tuple(weight.shape)}")
-    if weight.dtype != torch.float32 or not weight.is_contiguous():
-        raise RuntimeError(f"weight must be a contiguous float32 tensor, got {weight.dtype}")
-    c_out = int(weight.shape[0])
-    if weight.shape[1] != c0 + c1:
-        raise RuntimeError(f"weight takes {weight.shape[1]} input channels but the sources bring c0 + c1 = {c0} + {c1}")
-    if batch < 1 or not 1 <= side <= MAX_SIDE or side0 > MAX_SIDE or not 1 <= c0 + c1 <= MAX_CHANNELS or not 1 <= c_out <= MAX_CHANNELS:
-        raise RuntimeError(f"batch >= 1, sides 1 .. {MAX_SIDE} and channels 1 .. {MAX_CHANNELS} are covered, got batch {batch}, "
-                           f"sides {side0} -> {side}, channels {c0} + {c1} -> {c_out}")
+    batch, c0, side0, side, c1, c_out = _conv_args(x0, weight, bias, side, x1)
     if -(-side // side0) > MAX_ENLARGEMENT:
         raise RuntimeError(f"enlargements above {MAX_ENLARGEMENT} x are not covered in training mode, got {side0} -> {side}")
-    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != c_out):
-        raise RuntimeError(f"bias must be float32 with {c_out} elements, got {tuple(bias.shape)} {bias.dtype}")
-    gamma, beta, mean, var, eps, momentum, module = _bn_train_parts(bn, c_out)
+    gamma, beta, mean, var, eps, momentum, module = _bn_parts(bn, c_out, training=True)
     if batch * side * side == 1:
         raise ValueError(f"Expected more than 1 value per channel when training, got input size {(batch, c_out, side, side)}")
-    _check(x0, "x0")
-    _on_current_device(x0, "x0")
-    for t, name in ((x1, "x1"), (weight, "weight"), (bias, "bias"), (gamma, "bn weight"), (beta, "bn bias"),
-                    (mean, "bn running_mean"), (var, "bn running_var")):
-        if t is not None:
-            _check(t, name, device=x0.device)
+    _conv_on_device(x0, x1, weight, bias, gamma, beta, mean, var)
     y = _Conv3x3ReluBnTrain.apply(x0, x1, weight, bias, gamma, beta, (mean, var), eps, momentum, side)
     if module is not None and module.num_batches_tracked is not None:
         module.num_batches_tracked.add_(1)
@@ -272,15 +249,8 @@ class _AdaptiveMaxPoolTrain(torch.autograd.Function):
 
 
 def adaptive_max_pool_train(x: torch.Tensor, side_out: int) -> torch.Tensor:
-    """`adaptive_max_pool` (the same bits) with a backward: the forward also writes every window's first maximum in row-major
-    order (eg_adaptive_max_pool_idx_fwd), the backward gathers (eg_adaptive_max_pool_bwd)."""
-    _square_map(x, "x")
-    side_out = int(side_out)
-    side_in = int(x.shape[2])
-    if not 1 <= side_out <= side_in <= MAX_SIDE:
-        raise RuntimeError(f"side_out must be in 1 .. side_in = {side_in} <= {MAX_SIDE}, got {side_out}")
-    if int(x.shape[0]) * int(x.shape[1]) < 1:
-        raise RuntimeError("x has no planes")
-    _check(x, "x")
-    _on_current_device(x, "x")
+    """`adaptive_max_pool` (the same kernel, the same bits) with a backward: the forward also writes every window's first maximum
+    in row-major order (eg_adaptive_max_pool_idx_fwd), the backward gathers (eg_adaptive_max_pool_bwd)."""
+    side_out = _pool_args(x, side_out)
+    _on_device(x, "x")
     return _AdaptiveMaxPoolTrain.apply(x, side_out)

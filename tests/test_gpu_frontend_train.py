@@ -293,6 +293,41 @@ def test_pool_backward_is_torchs(side_in, side_out, planes, ties):
     assert torch.equal(xd.grad.cpu(), xc.grad)
 
 
+@pytest.mark.parametrize("side_in,side_out,planes", [(7, 3, 1), (5, 5, 1), (4, 2, 37), (17, 16, 3)])
+def test_both_pools_are_one_kernel(side_in, side_out, planes):
+    """The eval and the training pool are two instantiations of one kernel: the same bits out (compared as int32, since
+    torch.equal calls a NaN unequal to itself), and the saved indices are those of torch's CPU pool.  In every plane the first
+    window holds its maximum twice, at its first and its last element (not at 5 -> 5, where a window is one pixel), the last
+    window holds a NaN, and in plane 0 the window before it holds two.  Checked on the CPU: torch lets every NaN take over
+    (`val > max || isnan(val)`), so a NaN window's index is its LAST NaN -- the first where there is one -- which is the kernel's
+    rule as well: all windows are compared, the NaN windows included."""
+    g = torch.Generator().manual_seed(side_in * 100 + side_out)
+    x = torch.randn(2, planes, side_in, side_in, generator=g)
+    lo = lambda i: (i * side_in) // side_out
+    hi = lambda i: -(-(i + 1) * side_in // side_out)
+    tied = hi(0) - lo(0) > 1
+    if tied:
+        x[:, :, 0, 0] = x[:, :, hi(0) - 1, hi(0) - 1] = 50.0
+    last, nan = side_out - 1, float("nan")
+    x[:, :, hi(last) - 1, hi(last) - 1] = nan
+    x[0, 0, lo(last - 1), lo(last)] = x[0, 0, lo(last - 1), hi(last) - 1 if tied else lo(last)] = nan     # window (last - 1, last)
+    want, want_idx = F.adaptive_max_pool2d(x, side_out, return_indices=True)
+    assert bool(want[:, :, last, last].isnan().all()) and bool(want[0, 0, last - 1, last].isnan())
+    assert bool((want_idx[:, :, last, last] == (hi(last) - 1) * side_in + hi(last) - 1).all())
+    assert int(want_idx[0, 0, last - 1, last]) == lo(last - 1) * side_in + (hi(last) - 1 if tied else lo(last))       # the last NaN
+    if tied:
+        assert bool((want[:, :, 0, 0] == 50.0).all()) and bool((want_idx[:, :, 0, 0] == 0).all())      # the first of the two
+    xd = x.to(DEV)
+    got = ops.adaptive_max_pool_train(xd.clone().requires_grad_(), side_out)
+    with torch.no_grad():
+        plain = ops.adaptive_max_pool(xd, side_out)
+    idx, = got.grad_fn.saved_tensors
+    assert got.dtype == plain.dtype == torch.float32 and idx.dtype == torch.int32
+    assert torch.equal(got.detach().view(torch.int32), plain.view(torch.int32))
+    assert torch.equal(plain.cpu().isnan(), want.isnan()) and torch.equal(plain.cpu().nan_to_num(nan=0.0), want.nan_to_num(nan=0.0))
+    assert torch.equal(idx.cpu().long(), want_idx)
+
+
 # ---------------------------------------------------------------------------
 # the whole front-end
 # ---------------------------------------------------------------------------
