@@ -390,7 +390,10 @@ int eg_classifier_bwd_sums(const float* dlogits, const float* h, int batch, int6
 /* recompute_h != 0 (round 6): the layer's output h = act(z) + residual was never written in full (eg_classifier_train_fwd_act with
  * h_sparse: only the rows the heads' filter drops reach memory) -- `h` is ignored (may be NULL) and the first-layers kernel rebuilds
  * its h tile from layer_z (which it reads for the sums anyway) and layer_residual (the layer's input rows; NULL: no residual)
- * with the forward's own expression and dropout mask: 1.18 GB less written per step at batch 32.  Arrays below 2 GB. */
+ * with the forward's own expression and dropout mask: 1.18 GB less written per step at batch 32.  Arrays below 2 GB.
+ * At 2 GiB per array and more (batch 59+ at 224 / 7) recompute_h returns EG_ERR_UNSUPPORTED before anything is launched and this entry
+ * point, like eg_classifier_bwd, runs the flat-address form of its first-layers kernel; tested up to arrays below 4 GiB
+ * (tests/test_gpu_big_arrays.py: batch 59 / 60), not at 2^31 elements and more. */
 int eg_gcn_layer_bwd_presummed(const eg_graph* g_bwd, int batch, const float* dy, const float* z, const float* agg, const float* W,
                                const float* gamma, const float* beta, const float* bn, int relu, float dropout_p, uint64_t seed,
                                int residual, void* workspace, float* dz_scratch, float* dx, float* dw, float* db, float* dgamma,

@@ -138,26 +138,40 @@ def test_round_trip_properties_at_full_size():
     assert torch.equal(a[3 * nv:4 * nv], c)
 
 
-def _full_size_properties(frame, naux, B, main_only=False, layers=3, seed=5):
+def _device_node_feats(rows, seed):
+    """synthetic_node_feats' distribution drawn ON the device (a batch of 2 GB and more is not made with numpy and pushed through the host)."""
+    g = torch.Generator(DEV)
+    g.manual_seed(seed)
+    return torch.randn(rows, 128, generator=g, device=DEV)
+
+
+def _full_size_properties(frame, naux, B, main_only=False, layers=3, seed=5, f=None, alone=(), coord=False, device_inputs=False):
     """Size-independent checks at a BASELINE config's full per-GPU batch: linearity and symmetry of the aggregation,
-    frame independence, determinism of the whole stack, and one frame of the batch against the CPU oracle."""
+    frame independence, determinism of the whole stack, and one frame of the batch against the CPU oracle.
+    f: the frame that is run alone and against the oracle (default: the last but one); alone: further frames that must equal their
+    run alone bit for bit; coord: the same frames once more through the model WITH the coordinate graph (logits and coordinates of a
+    frame of the batch == the frame alone: the coordinate update's taps); device_inputs: features and edge_index made on the device."""
     from echoglad_amd import ops
     g = ops.Graph.topo(frame, naux, main_only)
     n = g.num_nodes
-    x = synthetic_node_feats(B * n, 128, seed=3).to(DEV)
-    y = synthetic_node_feats(B * n, 128, seed=4).to(DEV)
+    feats = _device_node_feats if device_inputs else (lambda rows, sd: synthetic_node_feats(rows, 128, seed=sd).to(DEV))
+    x = feats(B * n, 3)
+    y = feats(B * n, 4)
     ax, ay = ops.gcn_aggregate(g, B, x), ops.gcn_aggregate(g, B, y)
     axy = ops.gcn_aggregate(g, B, 2.0 * x - 0.5 * y)
     assert (axy - (2.0 * ax - 0.5 * ay)).abs().max() < 1e-4
     lhs, rhs = (ax.double() * y.double()).sum(), (x.double() * ay.double()).sum()
     assert abs(lhs - rhs) / abs(lhs) < 1e-6
-    f = B - 2
-    one = ops.gcn_aggregate(g, 1, x[f * n:(f + 1) * n].contiguous())
-    assert torch.equal(one, ax[f * n:(f + 1) * n])
+    f = B - 2 if f is None else f
+    for k in (f,) + tuple(alone):
+        one = ops.gcn_aggregate(g, 1, x[k * n:(k + 1) * n].contiguous())
+        assert torch.equal(one, ax[k * n:(k + 1) * n]), k
     del ax, ay, axy, y
     hip, ref = model_pair(frame, naux, layers, main_only=main_only, seed=seed)
-    topo, ei, nt, bi = graph_tensors(frame, naux, B, main_only=main_only)
+    topo, ei, nt, bi = graph_tensors(frame, naux, 1 if device_inputs else B, main_only=main_only)
     ei1 = torch.from_numpy(topo.edge_index())
+    if device_inputs:          # the batched edge_index: frame b's edges are frame 0's + b * n
+        ei = (ei1.to(DEV)[:, None, :] + (torch.arange(B, device=DEV) * n)[None, :, None]).reshape(2, -1).contiguous()
     with torch.no_grad():
         a, _ = hip.forward_nodes(x, ei.to(DEV), B)
         b, _ = hip.forward_nodes(x, ei.to(DEV), B)
@@ -166,6 +180,10 @@ def _full_size_properties(frame, naux, B, main_only=False, layers=3, seed=5):
     assert torch.equal(a, b)
     nv = topo.num_valid_nodes
     assert torch.equal(a[f * nv:(f + 1) * nv], c)
+    for k in alone:
+        with torch.no_grad():
+            ck, _ = hip.forward_nodes(x[k * n:(k + 1) * n].contiguous(), ei1.to(DEV), 1)
+        assert torch.equal(a[k * nv:(k + 1) * nv], ck), k
     assert (c.cpu() - want).abs().max() < TOL
     assert torch.equal(O.landmark_argmax(c.cpu(), 1, frame), O.landmark_argmax(want, 1, frame))
     # the HIP-graph replay path (what bench.py times) gives the same bits
@@ -182,6 +200,25 @@ def _full_size_properties(frame, naux, B, main_only=False, layers=3, seed=5):
         r1 = hip.forward_nodes(x1, e1, 1)[0].clone()
         r2 = hip.forward_nodes(x1, e1, 1)[0].clone()
     assert torch.equal(r1, c) and torch.equal(r2, c)
+    if not coord:
+        return
+    del hip, a, b, c, d, e, x, x1, r1, r2
+    # ---- with the coordinate graph (eval mode, statistics frozen): a frame of the batch == the same frame alone, logits AND coordinates
+    # (test_gpu_train.test_cfg4_train_full_batch_32_properties' last block, here for the far frames)
+    hip, _ = model_pair(frame, naux, layers, coord=True, seed=seed)
+    topo = graph_tensors(frame, naux, 1, coord=True)[0]
+    n, nv = topo.num_nodes, topo.num_valid_nodes
+    ei1 = torch.from_numpy(topo.edge_index()).to(DEV)
+    ei = (ei1[:, None, :] + (torch.arange(B, device=DEV) * n)[None, :, None]).reshape(2, -1).contiguous()
+    x = feats(B * n, 6)
+    jitter = torch.from_numpy(np.random.RandomState(9).uniform(-20, 20, (B * 4, 2)).astype(np.float32))
+    coords0 = (initial_coords(B, frame) + jitter).clamp(0, frame - 1).to(DEV)       # a different landmark set per frame
+    with torch.no_grad():
+        full, cfull = hip.forward_nodes(x, ei, B, coords0.clone())
+        for k in (f,) + tuple(alone):
+            one, cone = hip.forward_nodes(x[k * n:(k + 1) * n].contiguous(), ei1, 1, coords0.view(B, 4, 2)[k:k + 1].reshape(4, 2).clone())
+            assert torch.equal(full[k * nv:(k + 1) * nv], one), k
+            assert torch.equal(cfull.view(B, 4, 2)[k], cone.view(4, 2)), k
 
 
 def test_cfg2_default_full_batch_8_graph_replay_vs_oracle():
