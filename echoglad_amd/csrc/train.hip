@@ -665,7 +665,9 @@ unsigned* eg_ticket_ptr(void* stream, int slot) {
     if (!p) {
         unsigned* q = nullptr;
         if (hipMalloc((void**)&q, EG_TICKET_SLOTS * sizeof(unsigned)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        if (hipMemset(q, 0, EG_TICKET_SLOTS * sizeof(unsigned)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(q); return nullptr; }
+        // zeroed ON the stream whose launches will count on it: a hipMemset runs on the null stream, which a non-blocking stream does
+        // not wait for, so the first launch could start counting on a word that was cleared under it (a lost "last workgroup out")
+        if (hipMemsetAsync(q, 0, EG_TICKET_SLOTS * sizeof(unsigned), (hipStream_t)stream) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(q); return nullptr; }
         p = q;
     }
     return p + slot;

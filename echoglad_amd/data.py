@@ -95,21 +95,81 @@ def draw_coords(frame_size: int, orig_frame_size: int = 224, rng=np.random) -> n
                      [ivs[1] - 1, ivs[0] - 1]])
 
 
+def affine_matrix(tx=0.0, ty=0.0, sx=1.0, sy=1.0, rotation_theta=0.0, shear_theta=0.0):
+    """datasets.py:155-179 (``get_affine_matrix``): ``shear @ scale @ rotate @ translate`` on normalised (h, w), built and inverted
+    in fp64 -> (forward, inverse), each the upper two rows [A | b] as float32 [2, 3].  The forward matrix moves the landmarks, the
+    inverse one drives the image warp (datasets.py:208-233)."""
+    c, s = np.cos(rotation_theta), np.sin(rotation_theta)
+    rotate = np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
+    translate = np.array([[1.0, 0.0, tx], [0.0, 1.0, ty], [0.0, 0.0, 1.0]])
+    scale = np.array([[sx, 0.0, 0.0], [0.0, sy, 0.0], [0.0, 0.0, 1.0]])
+    shear = np.array([[1.0, -np.sin(shear_theta), 0.0], [0.0, np.cos(shear_theta), 0.0], [0.0, 0.0, 1.0]])
+    m = shear @ scale @ rotate @ translate
+    return m[:2].astype(np.float32), np.linalg.inv(m)[:2].astype(np.float32)
+
+
+def prep_coords(coords, frame_size: int, matrix=None, crop_size: Optional[int] = None, warp_size: int = 0, flip=None) -> np.ndarray:
+    """The landmark rule of eg_frame_prep on the host, numpy fp64: coords [B, 4, 2] (h, w) -> int32 [B, 4, 2].
+    With a warp stage (warp_size = W > 0; datasets.py:232-236), per axis: n = c * 2 / crop_size - 1, n' = A n + b with
+    matrix [B, 2, 3], q = (n' + 1) * W / 2 * F / W.  Without one q = c (frame-space integers already).  Then q is truncated toward
+    zero (``astype('int')``; saturating at the int32 range, NaN gives the smallest int32) and, where flip [B] is set,
+    w <- F - w - 1 (hflip's ``coords[:, 1] = F - coords[:, 1] - 1``)."""
+    c = np.asarray(coords, dtype=np.float64).reshape(-1, 4, 2)
+    F, W = int(frame_size), int(warp_size)
+    if W > 0:
+        if matrix is None or crop_size is None:
+            raise ValueError("a warp stage needs matrix and crop_size")
+        m = np.asarray(matrix, dtype=np.float64).reshape(-1, 2, 3)
+        n = c * 2.0 / float(crop_size) - 1.0
+        t = n @ m[:, :, :2].transpose(0, 2, 1) + m[:, None, :, 2]
+        c = (t + 1.0) * float(W) / 2.0 * float(F) / float(W)
+    lo, hi = float(np.iinfo(np.int32).min), float(np.iinfo(np.int32).max)
+    with np.errstate(invalid="ignore"):
+        q = np.where(np.isnan(c), lo, np.clip(c, lo, hi))
+    out = np.trunc(q).astype(np.int64)
+    if flip is not None:
+        f = np.asarray(flip).reshape(-1).astype(bool)
+        out[f, :, 1] = F - out[f, :, 1] - 1
+    return np.clip(out, int(lo), int(hi)).astype(np.int32)
+
+
 class SyntheticEchoDataset(torch.utils.data.Dataset):
     """Counterpart of ``DummyDataset``: 100 samples of N(0,1) frames with random landmark labels on the static
     hierarchical graph.  ``transform`` maps the [1, 224, 224] frame to [1, F, F] (default: bilinear resize).
 
     ``labels="coords"``: a sample carries ``label_coords`` (int32 [4, 2], the landmarks' (h, w)) and ``label_valid`` (float32 [4])
     instead of the dense ``y`` / ``valid_labels`` -- same random draws, same landmarks; ``device_labels_`` expands them on the
-    device."""
+    device.
+
+    ``frames="raw"``: a sample carries what a dataset READS instead of what it prepares -- ``raw_frame`` (uint8 [1, C, S, S], S =
+    ``crop_size``, C = 3 with ``make_gray`` else 1), ``raw_coords`` (float32 [4, 2], (h, w) in crop pixels with a warp stage,
+    frame-space integers without one), ``prep_flip`` (uint8, 1 with probability ``flip_p``) and, with ``warp_size`` > 0,
+    ``prep_matrix`` / ``prep_matrix_inv`` (float32 [2, 3], ``affine_matrix`` at scale crop / warp; ``augment`` = {"rotation": (lo, hi),
+    "shear": (lo, hi), "translation": (lo, hi)} draws the other parameters on the host).  It has no ``x``; with ``labels="coords"`` it
+    has no ``label_coords`` / ``node_coord_y`` either: ``device_frames_`` writes all three on the device (``transform`` is not used).
+    With ``labels="dense"`` the landmarks are prepared on the host (``prep_coords``) as before.  The default ``frames="prepared"``
+    is the behaviour described first, random draw for random draw."""
 
     def __init__(self, num_aux_graphs: int, frame_size: int = 128, transform=None, average_coords=None,
                  main_graph_type: str = "grid", aux_graph_type: str = "grid", use_coordinate_graph: bool = False,
                  use_connection_nodes: bool = False, use_main_graph_only: bool = False, length: int = 100,
-                 labels: str = "dense"):
+                 labels: str = "dense", frames: str = "prepared", crop_size: int = 224, warp_size: int = 0, flip_p: float = 0.0,
+                 make_gray: bool = False, augment=None):
         if labels not in ("dense", "coords"):
             raise ValueError(f"labels must be 'dense' or 'coords', got {labels!r}")
+        if frames not in ("prepared", "raw"):
+            raise ValueError(f"frames must be 'prepared' or 'raw', got {frames!r}")
+        if frames == "raw" and (int(crop_size) < 1 or int(warp_size) < 0 or not 0.0 <= float(flip_p) <= 1.0):
+            raise ValueError("raw frames need crop_size >= 1, warp_size >= 0 and flip_p in [0, 1]")
+        if augment and not int(warp_size) > 0:
+            raise ValueError("augment draws the warp's parameters: it needs warp_size > 0")
+        unknown = set(augment or {}) - {"rotation", "shear", "translation"}
+        if unknown:
+            raise ValueError(f"augment takes ranges for rotation, shear and translation, got {sorted(unknown)}")
         self.labels = labels
+        self.frames = frames
+        self.crop_size, self.warp_size, self.flip_p, self.make_gray = int(crop_size), int(warp_size), float(flip_p), bool(make_gray)
+        self.augment = dict(augment or {})
         self.spec = TopologySpec(frame_size, num_aux_graphs, use_main_graph_only, use_coordinate_graph,
                                  use_connection_nodes, main_graph_type, aux_graph_type)
         self.topology: HierTopology = get_topology(self.spec)
@@ -128,14 +188,37 @@ class SyntheticEchoDataset(torch.utils.data.Dataset):
     def __len__(self):
         return self.length
 
+    def _draw_raw(self, g):
+        """The raw part of a sample (frames="raw") -> the landmarks in frame space, prepared on the host (int [4, 2])."""
+        S, W, F = self.crop_size, self.warp_size, self.frame_size
+        g.raw_frame = torch.from_numpy(np.random.randint(0, 256, size=(1, 3 if self.make_gray else 1, S, S)).astype(np.uint8))
+        matrix = None
+        if W > 0:
+            # landmarks in the middle half of the crop: they stay inside the frame under a moderate warp
+            raw = np.random.uniform(0.25 * S, 0.75 * S, size=(4, 2)).astype(np.float32)
+            draw = lambda k: float(np.random.uniform(*self.augment[k])) if k in self.augment else 0.0
+            matrix, inverse = affine_matrix(tx=draw("translation"), ty=draw("translation"), sx=S / W, sy=S / W,
+                                            rotation_theta=draw("rotation"), shear_theta=draw("shear"))
+            g.prep_matrix, g.prep_matrix_inv = torch.from_numpy(matrix), torch.from_numpy(inverse)
+        else:
+            raw = np.maximum(draw_coords(F), 0).astype(np.float32)      # (no -1: flipped it would be F, outside every grid)
+        flip = np.uint8(np.random.uniform(0.0, 1.0) < self.flip_p)
+        g.raw_coords = torch.from_numpy(raw)
+        g.prep_flip = torch.tensor(flip, dtype=torch.uint8)
+        g.prep_crop_size, g.prep_warp_size, g.prep_frame_size, g.prep_gray = S, W, F, self.make_gray
+        return prep_coords(raw, F, matrix, S, W, [flip])[0].astype(int)
+
     def __getitem__(self, idx):
-        frame = self.transform(torch.randn((1, 224, 224))).unsqueeze(0)           # [1,1,F,F]
-        coords = draw_coords(self.frame_size)
         g = types.SimpleNamespace()
-        g.x = frame
+        if self.frames == "raw":
+            coords = self._draw_raw(g)
+        else:
+            g.x = self.transform(torch.randn((1, 224, 224))).unsqueeze(0)         # [1,1,F,F]
+            coords = draw_coords(self.frame_size)
         if self.labels == "coords":
             _check_label_coords(coords, self.frame_size)
-            g.label_coords = torch.from_numpy(coords.astype(np.int32))            # [4, 2]
+            if self.frames != "raw":                                              # (raw: device_frames_ writes them)
+                g.label_coords = torch.from_numpy(coords.astype(np.int32))        # [4, 2]
             g.label_valid = torch.ones(4, dtype=torch.float32)
             g.label_levels = self._label_levels
             g.label_frame_size = self.frame_size
@@ -148,7 +231,8 @@ class SyntheticEchoDataset(torch.utils.data.Dataset):
         g.num_nodes = self.topology.num_nodes
         if self.use_coordinate_graph and not self.use_main_graph_only:
             g.node_coords = torch.tensor(self.average_coords, dtype=torch.float32)
-            g.node_coord_y = torch.tensor(coords, dtype=torch.float32)
+            if self.frames != "raw" or self.labels != "coords":
+                g.node_coord_y = torch.tensor(coords, dtype=torch.float32)
         g.pix2mm_x = torch.tensor(0.1 * 10, dtype=torch.float32)
         g.pix2mm_y = torch.tensor(0.1 * 10, dtype=torch.float32)
         return g
@@ -162,10 +246,23 @@ def collate(samples: Sequence, topology: Optional[HierTopology] = None):
     n = samples[0].num_nodes
     out = types.SimpleNamespace()
     out.num_graphs = B
-    out.x = torch.cat([s.x for s in samples], dim=0)
-    if hasattr(samples[0], "label_coords"):
+    if hasattr(samples[0], "raw_frame"):
+        # raw frames: uint8 as read, the landmarks as annotated and the warp's matrices; device_frames_() prepares x (and, for
+        # coordinate labels, label_coords / node_coord_y) on the device
+        out.raw_frame = torch.cat([s.raw_frame for s in samples], dim=0)            # [B, C, S, S] uint8
+        out.raw_coords = torch.stack([s.raw_coords for s in samples])              # [B, 4, 2]
+        out.prep_flip = torch.stack([s.prep_flip for s in samples])                # [B] uint8
+        if hasattr(samples[0], "prep_matrix"):
+            out.prep_matrix = torch.stack([s.prep_matrix for s in samples])        # [B, 2, 3]
+            out.prep_matrix_inv = torch.stack([s.prep_matrix_inv for s in samples])
+        for k in ("prep_crop_size", "prep_warp_size", "prep_frame_size", "prep_gray"):
+            setattr(out, k, getattr(samples[0], k))
+    else:
+        out.x = torch.cat([s.x for s in samples], dim=0)
+    if hasattr(samples[0], "label_levels"):
         # coordinate labels: 32 + 16 bytes per frame; device_labels_() expands them into y / valid_labels on the device
-        out.label_coords = torch.stack([s.label_coords for s in samples])          # [B, 4, 2] int32
+        if hasattr(samples[0], "label_coords"):
+            out.label_coords = torch.stack([s.label_coords for s in samples])      # [B, 4, 2] int32
         out.label_valid = torch.stack([s.label_valid for s in samples])            # [B, 4]
         out.label_levels = tuple(samples[0].label_levels)
         out.label_frame_size = int(samples[0].label_frame_size)
@@ -195,7 +292,8 @@ def collate(samples: Sequence, topology: Optional[HierTopology] = None):
         out.batch = torch.arange(B).repeat_interleave(n)
     if hasattr(samples[0], "node_coords"):
         out.node_coords = torch.cat([s.node_coords for s in samples], dim=0)
-        out.node_coord_y = torch.cat([s.node_coord_y for s in samples], dim=0)
+        if hasattr(samples[0], "node_coord_y"):
+            out.node_coord_y = torch.cat([s.node_coord_y for s in samples], dim=0)
     out.pix2mm_x = torch.stack([s.pix2mm_x for s in samples])
     out.pix2mm_y = torch.stack([s.pix2mm_y for s in samples])
     return out
@@ -253,13 +351,23 @@ def copy_batch_(dst, src):
 
     A coordinate-label source (``label_coords`` / ``label_valid``, 48 bytes per frame) leaves ``dst.y`` / ``dst.valid_labels``
     alone: ``device_labels_(dst)`` rewrites them on the device.  The device cannot raise for a coordinate outside the frame, so a
-    CPU ``label_coords`` is checked here with ``label_rows``' rule (IndexError) before anything is copied."""
+    CPU ``label_coords`` is checked here with ``label_rows``' rule (IndexError) before anything is copied.
+
+    A raw-frame source (``raw_frame``, ``raw_coords``, ``prep_matrix`` / ``prep_matrix_inv``, ``prep_flip``) is copied like any other
+    tensor attribute and leaves ``dst.x`` (and, with coordinate labels, ``dst.label_coords`` / ``dst.node_coord_y``) alone:
+    ``device_frames_(dst)`` rewrites them.  Its CPU ``raw_coords`` get the same range check, on ``prep_coords`` of them."""
     lc = getattr(src, "label_coords", None)
     if torch.is_tensor(lc) and lc.device.type == "cpu":
         frame_size = getattr(src, "label_frame_size", None) or getattr(dst, "label_frame_size", None)
         if frame_size is None:
             raise ValueError("a batch with label_coords needs label_frame_size (collate() records it)")
         _check_label_coords(lc.numpy(), int(frame_size))
+    rc = getattr(src, "raw_coords", None)
+    if torch.is_tensor(rc) and rc.device.type == "cpu" and hasattr(src, "label_levels"):
+        # raw landmarks of a coordinate-label batch: the same check on what eg_frame_prep will make of them
+        m = getattr(src, "prep_matrix", None)
+        _check_label_coords(prep_coords(rc.numpy(), src.prep_frame_size, None if m is None else m.cpu().numpy(), src.prep_crop_size,
+                                        src.prep_warp_size, src.prep_flip.cpu().numpy()), int(src.prep_frame_size))
     verified = dst.__dict__.setdefault("_graph_consts_verified", set())
     for k, v in vars(src).items():
         if not torch.is_tensor(v):
@@ -308,4 +416,38 @@ def device_labels_(batch):
         if valid is None:
             valid = batch.valid_labels = torch.empty(B * n_rows, 4, dtype=torch.float32, device=coords.device)
     ops.node_labels(coords, getattr(batch, "label_valid", None), B, levels, batch.label_frame_size, y, valid)
+    return batch
+
+
+def device_frames_(batch):
+    """Prepares ``batch.raw_frame`` (a batch of ``frames="raw"`` samples, on the device) into ``batch.x`` [B, C_out, F, F]: uint8 ->
+    float / 255, the affine warp, the bilinear resize, gray and the horizontal flip in one launch (ops.frame_prep), no host
+    synchronisation, so it can be the first node of a captured step, in front of ``device_labels_``.  A coordinate-label batch
+    (``label_levels``) also gets ``batch.label_coords`` [B, 4, 2] and, with coordinate nodes, ``batch.node_coord_y`` [B * 4, 2] from
+    ``batch.raw_coords`` through the same matrix and flip.  The outputs are allocated at the first (eager) call and rewritten in place
+    afterwards; inside a stream capture they must exist already.  A batch without ``raw_frame`` is returned as it is."""
+    raw = getattr(batch, "raw_frame", None)
+    if raw is None:
+        return batch
+    from . import ops
+    B, C = int(raw.shape[0]), int(raw.shape[1])
+    F, W, gray = int(batch.prep_frame_size), int(batch.prep_warp_size), bool(batch.prep_gray)
+    with_coords = getattr(batch, "label_levels", None) is not None
+    with_coord_y = with_coords and getattr(batch, "node_coords", None) is not None
+    x, lc, cy = getattr(batch, "x", None), getattr(batch, "label_coords", None), getattr(batch, "node_coord_y", None)
+    if x is None or (with_coords and lc is None) or (with_coord_y and cy is None):
+        if raw.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("device_frames_: batch.x / batch.label_coords / batch.node_coord_y do not exist yet and a stream capture "
+                               "must not allocate: call device_frames_(batch) once eagerly (a warm-up step does) before capturing")
+        if x is None:
+            x = batch.x = torch.empty(B, 1 if gray else C, F, F, dtype=torch.float32, device=raw.device)
+        if with_coords and lc is None:
+            lc = batch.label_coords = torch.empty(B, 4, 2, dtype=torch.int32, device=raw.device)
+        if with_coord_y and cy is None:
+            cy = batch.node_coord_y = torch.empty(4 * B, 2, dtype=torch.float32, device=raw.device)
+    ops.frame_prep(raw, x, matrix_inv=getattr(batch, "prep_matrix_inv", None) if W > 0 else None, warp_size=W,
+                   flip=getattr(batch, "prep_flip", None), gray=gray,
+                   coords=batch.raw_coords if with_coords else None, matrix=getattr(batch, "prep_matrix", None) if W > 0 else None,
+                   crop_size=int(batch.prep_crop_size), out_label_coords=lc if with_coords else None,
+                   out_coord_y=cy if with_coord_y else None)
     return batch

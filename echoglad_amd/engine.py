@@ -61,7 +61,12 @@ def total_loss(losses) -> torch.Tensor:
 
 def _device_labels(batch):
     """A batch of coordinate labels (``label_coords``, data.collate of ``labels="coords"`` samples): its dense ``y`` / ``valid_labels``
-    are written on the device first -- one launch, a node of the graph when the step is being captured."""
+    are written on the device first -- one launch, a node of the graph when the step is being captured.  A batch of raw frames
+    (``raw_frame``, ``frames="raw"`` samples) is prepared in front of that (``data.device_frames_``: x, and the label coordinates the
+    expansion reads), so preparation -> labels are the first two nodes of a captured step."""
+    if getattr(batch, "raw_frame", None) is not None:
+        from .data import device_frames_
+        device_frames_(batch)
     if getattr(batch, "label_coords", None) is not None:
         from .data import device_labels_
         device_labels_(batch)
@@ -202,7 +207,8 @@ class GraphedEvalStep:
 
     ``static_batch``: a collated batch on the device (``data.to_device``); write every new batch INTO it (``data.copy_batch_``) before
     calling the step; a static batch of coordinate labels (``label_coords``) has its dense labels rebuilt by the graph's first node
-    (``data.device_labels_``).  ``pix2mm_x / pix2mm_y`` must be device tensors.  The graph reads ``static_batch.node_coords`` into a private
+    (``data.device_labels_``), a static batch of raw frames (``raw_frame``) is prepared by the node in front of it
+    (``data.device_frames_``).  ``pix2mm_x / pix2mm_y`` must be device tensors.  The graph reads ``static_batch.node_coords`` into a private
     buffer first: the caller's tensor is never written.  ``step()`` -> (preds, coord_preds, losses), the graph's static outputs, valid
     until the next call.  ``loss_avg()`` is the reference's ``loss_meter.avg`` (meters.AverageEpochMeter: an fp64 sum of
     ``total_loss * batch_size`` over an fp64 count, kept on the device and read back only there); ``reset_meter()`` zeroes it.
@@ -239,7 +245,7 @@ class GraphedEvalStep:
         self.model, self.criterion, self.batch_size = model, criterion, int(batch_size)
         self.use_coordinate_graph, self.evaluators, self.warmup = bool(use_coordinate_graph), evaluators, int(warmup)
         self.static_batch = static_batch
-        device = static_batch.x.device
+        device = (static_batch.raw_frame if getattr(static_batch, "x", None) is None else static_batch.x).device
         # the graph's own view of the batch: the caller's tensors, but node_coords through a private buffer the graph refills
         self._batch = copy.copy(static_batch)
         self._coords = None

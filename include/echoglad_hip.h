@@ -91,8 +91,8 @@ extern "C" {
  * 143: eg_landmark_record_workspace_bytes, eg_landmark_record_hm, eg_landmark_record_coord.  144: eg_node_labels.
  * 145: eg_conv3x3_relu_bn_fwd, eg_adaptive_max_pool_fwd.
  * 146: eg_frontend_train_workspace_bytes, eg_conv3x3_relu_fwd, eg_bn2d_train_fwd, eg_relu_bn2d_bwd, eg_conv3x3_bwd_data,
- * eg_conv3x3_bwd_weight, eg_adaptive_max_pool_idx_fwd, eg_adaptive_max_pool_bwd. */
-#define EG_ABI_VERSION 146
+ * eg_conv3x3_bwd_weight, eg_adaptive_max_pool_idx_fwd, eg_adaptive_max_pool_bwd.  147: eg_frame_prep. */
+#define EG_ABI_VERSION 147
 
 #define EG_CHANNELS 128 /* node_embedding_dim == node_hidden_dim (configs/default.yml:13-14) */
 
@@ -669,6 +669,38 @@ int eg_landmark_record_coord(const float* coord_pred, const float* coord_y, int 
  * is not frame_size, NULL coords or labels, misaligned labels / valid. */
 int eg_node_labels(const int* coords, const float* valid4, int batch, int64_t n_rows, const int* level_start, const int* level_side,
                    int n_levels, int frame_size, float* labels, float* valid, eg_stream_t stream);
+
+/* ---- frame preparation (reference: src/core/datasets.py, frame.float().div(255), UICLVLandmark.transform_image :317-349, the
+ * landmarks through the same matrix :232-236, dataset_builder's Resize((F, F)) / Grayscale, hflip with probability flip_p) ------
+ * What a dataset does per sample on the host between "a frame was read" and "x / coords exist", for a batch:
+ *   src [batch, channels, src_h, src_w] uint8 (src_is_u8 != 0) or float32, channels 1 or 3
+ *   out [batch, C_out, F, F] float32, F = frame_size, C_out = 1 when gray (channels must be 3 then), else channels
+ *   matrix_inv, matrix_fwd [batch, 2, 3] float32 [A | b], acting on normalised (h, w) in [-1, 1]
+ *   flip [batch] bytes, or NULL (no flip)
+ *   warp_size = W > 0: a warp stage to a W x W image; matrix_inv must be given.  W = 0: none; matrix_inv must be NULL.
+ *   coords_in [batch, 4, 2] float32 (h, w), or NULL: no coordinate part (matrix_fwd, crop_size, label_coords, coord_y are ignored)
+ *   label_coords [batch, 4, 2] int32;  coord_y [batch * 4, 2] float32, or NULL
+ * Pixels.  v(c, y, x) = src / 255 (a division) for uint8, src itself for float32; 0 outside [0, src_h) x [0, src_w).
+ *   warped(c, i, j), 0 <= i, j < W (affine_grid + grid_sample(bilinear, zeros, align_corners=False) as transform_image drives them):
+ *     n_h = (2 i + 1) / W - 1, n_w = (2 j + 1) / W - 1;   s_h = A00 n_h + A01 n_w + b0, s_w = A10 n_h + A11 n_w + b1 with matrix_inv
+ *     y = ((s_h + 1) src_h - 1) / 2, x = ((s_w + 1) src_w - 1) / 2, y0 = floor(y), x0 = floor(x), fy = y - y0, fx = x - x0
+ *     warped = (1-fy)(1-fx) v(y0, x0) + (1-fy) fx v(y0, x0+1) + fy (1-fx) v(y0+1, x0) + fy fx v(y0+1, x0+1)
+ *   without a warp stage warped = v, of sides src_h x src_w.
+ *   resized(c, i, j), 0 <= i, j < F (interpolate(bilinear, align_corners=False), no antialiasing), per axis over a side S of warped:
+ *     s = max((o + 0.5) S / F - 0.5, 0), i0 = floor(s), i1 = min(i0 + 1, S - 1), l = s - i0;  the four-tap blend of warped.
+ *   gray (after the resize): 0.2989 R + 0.587 G + 0.114 B.
+ *   out[b, c, i, flip[b] ? F - 1 - j : j] = resized(c, i, j).
+ *   Tap positions are computed in fp64, weights and blends in fp32; the W x W image is never materialised.
+ * Landmarks (fp64).  With a warp stage, for c = coords_in[b, k] in crop pixels, per axis: n = c 2 / crop_size - 1,
+ *   n' = A n + b with matrix_fwd, q = (n' + 1) W / 2 * F / W.  Without one q = c.  label_coords = (int) q, toward zero (saturating;
+ *   NaN gives INT_MIN); then, where flip[b], w <- F - w - 1.  coord_y holds the same integers as float32.
+ * ONE launch; every output element is written exactly once (no atomics: the same bits from run to run); no allocation, no
+ * synchronisation: capturable.  EG_ERR_ARG, nothing launched: a size < 1 or a side above 32768, channels not 1 or 3, gray without 3
+ * channels, warp_size < 0, matrix_inv missing with or given without a warp stage, NULL src / out, coords_in without label_coords or
+ * (with a warp stage) without matrix_fwd / crop_size >= 1, a misaligned float pointer, batch * F^2 too large for one grid. */
+int eg_frame_prep(const void* src, int src_is_u8, int batch, int channels, int src_h, int src_w, const float* matrix_inv,
+                  int warp_size, int frame_size, const unsigned char* flip, int gray, float* out, const float* coords_in,
+                  const float* matrix_fwd, int crop_size, int* label_coords, float* coord_y, eg_stream_t stream);
 
 /* ---- UNet front-end, inference (reference: DownConv / UpConv, src/core/models.py:841-876, in eval mode) ---------------------
  * fp32 NCHW, contiguous, square maps of side 1 .. 512 with 1 .. 512 channels; 4-byte alignment is enough.
