@@ -242,7 +242,9 @@ __global__ __launch_bounds__(HM_THREADS) void k_hm_partial(const float* __restri
         const int h = r / side, w = r - h * side;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            const double e = (double)expf(xv[c] - m[c]);
+            // (a chunk whose logits are all -inf has the maximum -inf: -inf - -inf is NaN, and NaN * 0 in the merge poisoned the whole
+            //  level.  Such a chunk holds no mass -- torch.softmax's answer; a finite maximum leaves every bit as it was)
+            const double e = m[c] == NEG ? 0.0 : (double)expf(xv[c] - m[c]);
             s[c] += e; sh[c] += e * h; sw[c] += e * w;
         }
     }

@@ -66,7 +66,8 @@ def test_evaluator_matches_reference_fixture(golden_dir, name):
 
 @pytest.mark.parametrize("frame,naux,batch", [(224, 7, 2), (64, 6, 3), (17, 3, 2)])
 def test_decode_and_losses_vs_oracle_at_full_size(frame, naux, batch):
-    """BASELINE-size frames (50,176-node main grid = 25 chunks per level): same numbers as the CPU oracle."""
+    """BASELINE-size frames (50,176-node main grid = 49 chunks of 1,024 rows: fewer than the 64 lanes of the final merge, whose
+    second round tests/test_gpu_heatmap_edges.py reaches): same numbers as the CPU oracle."""
     rs = np.random.RandomState(frame + naux)
     levels = LO.level_grids(frame, naux)
     n = levels[-1][0] + frame * frame
