@@ -297,7 +297,12 @@ struct ClsArgs {
     float* logits;
     int sigmoid;
     int row_lo, n_valid;        // the heads' node-type filter: rows [row_lo, row_lo + n_valid) of a frame have a logits row (logits is [batch * n_valid, 4])
+    // the last layer folded into the heads' first product (k_gcn_layer_ps FOLD, eg_gcn_layer_cls_fold_fwd): the launch's W is
+    // M = diag(s1) W1 diag(s) W, w1 is W1s = diag(s1) W1, t1 is c = s1 (W1 t) + t1, s1 is not read.  (In the struct's tail
+    // padding: the kernels' argument layout is what it was.)
+    int fold;
 };
+static_assert(sizeof(ClsArgs) == 9 * sizeof(void*) + 4 * sizeof(int), "ClsArgs: fold sits in what used to be padding");
 }  // namespace eg
 namespace eg {
 // dX launch that ALSO takes the BatchNorm-backward sums of the layer BELOW (k_gcn_layer_ps MODE 3): its output rows are that

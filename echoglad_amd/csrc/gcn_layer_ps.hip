@@ -135,7 +135,12 @@ __device__ inline void ps_claim(int* __restrict__ counters, int group, int n_til
 // as jk_in); with the classifier heads fused in, the heads run on max(jk_in, out) instead of out.
 // DIAG: the handle has 'grid-diagonal' levels (8-neighbour grids); their segment pairs aggregate through segp_diag_rows, and
 // the rare node-by-node path reads the handle's per-frame CSR (rowptr / colidx) instead of decoding the plain stencil.
-template <bool CLS, bool JK = false, int MODE = 0, bool DIAG = false>
+// FOLD (with CLS, without JK): the last layer runs without ReLU, so the heads' first pre-activation is linear in the two tiles
+// the producers leave in LDS,  u = (A_hat h) M^T + r h W1s^T + c  (nn/_heads.py fold_last_into_heads: M = diag(s1) W1 diag(s) W,
+// W1s = diag(s1) W1, c = s1 (W1 t) + t1).  FOLD = 1: r = 1, the layer has the residual; FOLD = 2: r = 0, no second product.
+// The caller passes M as W, W1s as ca.w1 and c as ca.t1; the layer's output tile is never formed: no epilogue between the
+// products, no write into s_x, and of s_bn only c is left.
+template <bool CLS, bool JK = false, int MODE = 0, bool DIAG = false, int FOLD = 0>
 __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __restrict__ x, const float* __restrict__ W,
                                                                 const float* __restrict__ scale, const float* __restrict__ shift,
                                                                 float* __restrict__ out, const float* __restrict__ dis,
@@ -156,7 +161,7 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
     int* s_cd = s_tile + 16;                          // [2][8 segments][4] descriptor words of the consumers' epilogue (below)
     float* s_dis0 = smem + PS_LDS_DIS;                // [2][TILE] (deg+1)^-1/2 of the tile's rows (child sums of the output)
     float* s_pat = smem + PS_LDS_PAT;                 // [n_pats][64] weight patterns, quad layout (seg_wide.h)
-    float* s_bn = s_pat + a.n_pats * PATQ;            // CLS only: [4][128] layer scale, shift, classifier s1, t1
+    float* s_bn = s_pat + a.n_pats * PATQ;            // CLS only: [4][128] layer scale, shift, classifier s1, t1; FOLD: [128] c
 
     const int tid = threadIdx.x;
     const int lane_k = tid & 63;
@@ -179,8 +184,11 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
     if (TRAIN) {    // rows of a tile that hold no node are masked out of the statistics by a factor 0: they must be finite
         for (int i = tid; i < 4 * TILE * LDA; i += PS_THREADS) smem[i] = 0.f;
     }
+    static_assert(!FOLD || (CLS && !JK && MODE == 0), "FOLD is a form of the fused last layer without the running maximum");
     if (CLS) {
-        if (tid < C) {
+        if (FOLD) {
+            if (tid < C) s_bn[tid] = ca.t1[tid];
+        } else if (tid < C) {
             s_bn[tid] = scale ? scale[tid] : 1.0f;
             s_bn[C + tid] = shift ? shift[tid] : 0.0f;
             s_bn[2 * C + tid] = ca.s1[tid];
@@ -200,7 +208,7 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
         // The per-channel scale of the epilogue (eval-mode BatchNorm folded by the caller) goes into the W slice -- lane
         // (i = l & 31) holds output channel 32 wave + i -- and the shift into the accumulators' initial value: the epilogue
         // is max + residual add, with no LDS or register operand of its own.
-        if (scale) {
+        if (!FOLD && scale) {                          // (FOLD: W is M, every scale is inside it)
             const float sv = scale[32 * wave + (lane_k & 31)];
 #pragma unroll
             for (int t = 0; t < 64; ++t) wreg[t] *= sv;
@@ -223,7 +231,7 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
         float b3v = 0.f;
         if (CLS) {
             load_w_slice(ca.w1, wave, lane_k, 0, wreg2);
-            {
+            if (!FOLD) {
                 const float sv = ca.s1[32 * wave + (lane_k & 31)];      // the first head layer's BatchNorm scale, folded the same way
 #pragma unroll
                 for (int t = 0; t < 64; ++t) wreg2[t] *= sv;
@@ -353,10 +361,10 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
                 store_data_guard(ks);
             };
             f32x16 acc0, acc1;
-            if (CLS) {                                  // (no registers for a persistent copy: the shift comes from LDS each tile)
+            if (CLS) {                                  // (no registers for a persistent copy: the shift -- FOLD: c -- comes from LDS each tile)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    const f32x4 q = *reinterpret_cast<const f32x4*>(s_bn + C + 32 * wave + 4 * (lane >> 5) + 8 * g);
+                    const f32x4 q = *reinterpret_cast<const f32x4*>(s_bn + (FOLD ? 0 : C) + 32 * wave + 4 * (lane >> 5) + 8 * g);
                     acc0[4 * g] = q.x; acc0[4 * g + 1] = q.y; acc0[4 * g + 2] = q.z; acc0[4 * g + 3] = q.w;
                 }
                 acc1 = acc0;
@@ -375,7 +383,9 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
             // residual rows of both 32-row blocks, read BEFORE the MFMA chains: an LDS wait inside a chain stalls the
             // wave's next MFMA as well (in-order issue)
             f32x4 res[2][4];
-            if (RES_LATE) {                                                   // one register set: rows 0..31 now, rows 32..63 once those are done
+            if (FOLD) {
+                // (the residual rows are the second product's operand)
+            } else if (RES_LATE) {                                            // one register set: rows 0..31 now, rows 32..63 once those are done
 #pragma unroll
                 for (int g = 0; g < 4; ++g) res[0][g] = *reinterpret_cast<const f32x4*>(s_x + j * LDA + 32 * wave + 4 * h + 8 * g);
             } else {
@@ -504,8 +514,10 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
             asm volatile("" : "+v"(acc1));
             __builtin_amdgcn_sched_barrier(0);
 #else
-            mfma_rowblock(s_a, 0, lane, wreg, acc0);
-            mfma_rowblock_with(s_a, 32, lane, wreg, acc1, between);
+            if (!FOLD) {                                   // (FOLD: all four products run as one pipeline, below)
+                mfma_rowblock(s_a, 0, lane, wreg, acc0);
+                mfma_rowblock_with(s_a, 32, lane, wreg, acc1, between);
+            }
 #endif
 #else
             acc0[0] += wreg[0] + s_a[lane]; acc1[0] += wreg[63];
@@ -521,8 +533,10 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
 #pragma unroll
             for (int g = EG_STAMP3; g < 4; ++g) finish_group(acc1, 1, g);
 #else
+            if (!FOLD) {
 #pragma unroll
-            for (int g = 0; g < 4; ++g) finish_group(acc1, 1, g);
+                for (int g = 0; g < 4; ++g) finish_group(acc1, 1, g);
+            }
 #endif
             if (!CLS) {
                 read_segments(4);
@@ -572,29 +586,89 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
                         }
                     }
                 }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                if (lane == 0) __hip_atomic_fetch_add(s_sync, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-                const int target = 4 * (k + 1);
-                while (__hip_atomic_load(s_sync, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < target) __builtin_amdgcn_s_sleep(1);
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                auto a_tile_done = [&]() {                 // this wave has read all it needs of the A tile ...
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                    if (lane == 0) __hip_atomic_fetch_add(s_sync, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                };
+                auto a_tile_free = [&]() {                 // ... and so have the other three
+                    const int target = 4 * (k + 1);
+                    while (__hip_atomic_load(s_sync, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < target) __builtin_amdgcn_s_sleep(1);
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                };
+                if (!FOLD) {
+                    a_tile_done();
+                    a_tile_free();
+                }
                 PSTAMP(2);                                 // (stamp builds: the consumers' wait for each other counts as barrier time)
                 // first layers: hidden[row][32 wave + c] = relu(bn(h3[row][:] . W1[32 wave + c][:])), into this wave's column
                 // slice of the A tile (dead now: every wave is past its MFMAs on it)
                 f32x16& hc0 = acc0;
                 f32x16& hc1 = acc1;
+                if (!FOLD) {
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {                      // start from the BatchNorm shift t1 (the scale s1 is in wreg2)
-                    const f32x4 q = *reinterpret_cast<const f32x4*>(s_bn + 3 * C + 32 * wave + 4 * h + 8 * g);
-                    hc0[4 * g] = q.x; hc0[4 * g + 1] = q.y; hc0[4 * g + 2] = q.z; hc0[4 * g + 3] = q.w;
-                }
-                hc1 = hc0;
+                    for (int g = 0; g < 4; ++g) {                  // start from the BatchNorm shift t1 (the scale s1 is in wreg2)
+                        const f32x4 q = *reinterpret_cast<const f32x4*>(s_bn + 3 * C + 32 * wave + 4 * h + 8 * g);
+                        hc0[4 * g] = q.x; hc0[4 * g + 1] = q.y; hc0[4 * g + 2] = q.z; hc0[4 * g + 3] = q.w;
+                    }
+                    hc1 = hc0;
+                }                                                  // (FOLD: the accumulators hold c + (A_hat h) M^T, the same chain goes on)
                 auto hidden_group = [&](const f32x16& hc, int rb, int g) {
                     f32x4 v = f32x4{hc[4 * g], hc[4 * g + 1], hc[4 * g + 2], hc[4 * g + 3]};
                     v.x = max_raw(v.x, 0.f); v.y = max_raw(v.y, 0.f); v.z = max_raw(v.z, 0.f); v.w = max_raw(v.w, 0.f);
                     *reinterpret_cast<f32x4*>(s_a + (32 * rb + j) * LDA + 32 * wave + 4 * h + 8 * g) = v;
                 };
-                mfma_rowblock(s_x, 0, lane, wreg2, hc0);
-                mfma_rowblock_with(s_x, 32, lane, wreg2, hc1, [&](int c) { hidden_group(hc0, 0, c); });
+                if (!FOLD) {
+                    mfma_rowblock(s_x, 0, lane, wreg2, hc0);
+                    mfma_rowblock_with(s_x, 32, lane, wreg2, hc1, [&](int c) { hidden_group(hc0, 0, c); });
+                } else {
+                    // FOLD: the four products -- rows 0..31 and 32..63 of s_a on M, then of s_x on W1s, into the same two accumulators
+                    // -- as ONE software pipeline: the first fragments of a product are read while the last chunk of the one before
+                    // runs, so only the tile's first read is exposed (mfma_rowblock drains at every start: ~130 cycles each).
+                    //
+                    // The meeting guards the A tile alone.  hidden_group writes this wave's column slice of s_a while the other three
+                    // waves may still be reading those columns in their own products over it, so a wave signals once its LAST fragment
+                    // of s_a is in registers (read a whole chunk earlier: the signal's fence finds nothing to wait for) and waits in
+                    // front of its FIRST hidden_group; both once per tile and unconditionally, so the count is 4 (k + 1) at every tile
+                    // barrier and nobody waits for a signal that is not sent.  The third product touches s_x only and gives the
+                    // others 64 MFMAs to arrive; the poll's LDS round trip runs beside the reads of the fourth product's fragments.
+                    const f32x4* pa = reinterpret_cast<const f32x4*>(s_a + j * LDA + 64 * h);
+                    const f32x4* px = reinterpret_cast<const f32x4*>(s_x + j * LDA + 64 * h);
+                    constexpr int R32 = 32 * LDA / 4;              // rows 32..63, in 16-byte units
+                    f32x4 a0[4], a1[4];
+                    auto ld = [&](f32x4 (&av)[4], const f32x4* p, int t0) {
+#pragma unroll
+                        for (int t = 0; t < 4; ++t) av[t] = p[t0 + t];
+                    };
+#define PS_STEP __builtin_amdgcn_sched_barrier(0)
+                    ld(a0, pa, 0); ld(a1, pa, 4); PS_STEP;
+                    mfma_chunk(a0, wreg, 0, acc0); PS_STEP; ld(a0, pa, 8); PS_STEP;
+                    mfma_chunk(a1, wreg, 4, acc0); PS_STEP; ld(a1, pa, 12); PS_STEP;
+                    mfma_chunk(a0, wreg, 8, acc0); PS_STEP; ld(a0, pa + R32, 0); PS_STEP;
+                    mfma_chunk(a1, wreg, 12, acc0); PS_STEP; ld(a1, pa + R32, 4); PS_STEP;
+                    mfma_chunk(a0, wreg, 0, acc1); PS_STEP; ld(a0, pa + R32, 8); PS_STEP;
+                    mfma_chunk(a1, wreg, 4, acc1); PS_STEP; ld(a1, pa + R32, 12); PS_STEP;      // (the last fragments of s_a)
+                    mfma_chunk(a0, wreg, 8, acc1); PS_STEP;
+                    a_tile_done(); PS_STEP;
+                    if (FOLD == 1) {
+                        ld(a0, px, 0); PS_STEP;
+                        mfma_chunk(a1, wreg, 12, acc1); PS_STEP; ld(a1, px, 4); PS_STEP;
+                        mfma_chunk(a0, wreg2, 0, acc0); PS_STEP; ld(a0, px, 8); PS_STEP;
+                        mfma_chunk(a1, wreg2, 4, acc0); PS_STEP; ld(a1, px, 12); PS_STEP;
+                        mfma_chunk(a0, wreg2, 8, acc0); PS_STEP; ld(a0, px + R32, 0); PS_STEP;
+                        mfma_chunk(a1, wreg2, 12, acc0); PS_STEP; ld(a1, px + R32, 4); PS_STEP;
+                        a_tile_free(); PS_STEP;
+                        mfma_chunk(a0, wreg2, 0, acc1); hidden_group(acc0, 0, 0); PS_STEP; ld(a0, px + R32, 8); PS_STEP;
+                        mfma_chunk(a1, wreg2, 4, acc1); hidden_group(acc0, 0, 1); PS_STEP; ld(a1, px + R32, 12); PS_STEP;
+                        mfma_chunk(a0, wreg2, 8, acc1); hidden_group(acc0, 0, 2); PS_STEP;
+                        mfma_chunk(a1, wreg2, 12, acc1); hidden_group(acc0, 0, 3);
+                    } else {                                       // (without a residual the products over s_a were all of it)
+                        mfma_chunk(a1, wreg, 12, acc1); PS_STEP;
+                        a_tile_free();
+#pragma unroll
+                        for (int g = 0; g < 4; ++g) hidden_group(acc0, 0, g);
+                    }
+#undef PS_STEP
+                }
                 PSTAMP(3);                                 // (stamp builds: the second GEMM counts as "loop")
                 const int j16 = lane & 15, kq = lane >> 4;
                 f32x4 hb[4][2];
@@ -948,7 +1022,10 @@ int eg_launch_layer_ps(const eg_graph* g, int batch, const float* x, const float
     if (lower) a.lower = *lower;
     const long long n_tiles = (long long)a.tiles_per_frame * batch;
     if (n_tiles <= 0) return EG_OK;
-    const size_t lds = (size_t)(PS_LDS_PAT + g->n_pats * PATQ + (cls ? 4 * C : 0)) * sizeof(float);      // (topo_tables.hip checks the same sum)
+    const bool fold = cls && cls->fold;                           // (gcn_layer.hip eg_gcn_layer_cls_fold_fwd: no running maximum, no ReLU)
+    if (fold && (jk || relu || scale || shift)) return set_error(EG_ERR_ARG, "the folded heads take no running maximum, ReLU, scale or shift");
+    // (the folded form keeps one vector in s_bn; topo_tables.hip checks the larger sum)
+    const size_t lds = (size_t)(PS_LDS_PAT + g->n_pats * PATQ + (fold ? C : cls ? 4 * C : 0)) * sizeof(float);
     if (lds > 160 * 1024) return EG_ERR_UNSUPPORTED;             // more weight patterns than fit beside the tile buffers
     {   // 160 KB of dynamic LDS needs the attribute once per device (idempotent, so a benign race sets it twice at worst)
         static std::atomic<bool> attr_set[64];
@@ -960,7 +1037,9 @@ int eg_launch_layer_ps(const eg_graph* g, int batch, const float* x, const float
                                      (const void*)k_gcn_layer_ps<false, false, 1>, (const void*)k_gcn_layer_ps<false, false, 2>,
                                      (const void*)k_gcn_layer_ps<false, false, 0, true>, (const void*)k_gcn_layer_ps<true, false, 0, true>,
                                      (const void*)k_gcn_layer_ps<false, false, 1, true>, (const void*)k_gcn_layer_ps<false, false, 2, true>,
-                                     (const void*)k_gcn_layer_ps<false, false, 3>, (const void*)k_gcn_layer_ps<false, false, 3, true>};
+                                     (const void*)k_gcn_layer_ps<false, false, 3>, (const void*)k_gcn_layer_ps<false, false, 3, true>,
+                                     (const void*)k_gcn_layer_ps<true, false, 0, false, 1>, (const void*)k_gcn_layer_ps<true, false, 0, true, 1>,
+                                     (const void*)k_gcn_layer_ps<true, false, 0, false, 2>, (const void*)k_gcn_layer_ps<true, false, 0, true, 2>};
             for (const void* f : kernels) EG_HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             if (dev >= 0 && dev < 64) attr_set[dev].store(true, std::memory_order_release);
         }
@@ -1012,11 +1091,13 @@ int eg_launch_layer_ps(const eg_graph* g, int batch, const float* x, const float
         if (train) launch(k_gcn_layer_ps<false, false, 1, true>);
         else if (rsep && lower) launch(k_gcn_layer_ps<false, false, 3, true>);
         else if (rsep) launch(k_gcn_layer_ps<false, false, 2, true>);
+        else if (fold) { if (residual) launch(k_gcn_layer_ps<true, false, 0, true, 1>); else launch(k_gcn_layer_ps<true, false, 0, true, 2>); }
         else if (cls) launch(k_gcn_layer_ps<true, false, 0, true>);
         else launch(k_gcn_layer_ps<false, false, 0, true>);
     } else if (train) launch(k_gcn_layer_ps<false, false, 1>);
     else if (rsep && lower) launch(k_gcn_layer_ps<false, false, 3>);
     else if (rsep) launch(k_gcn_layer_ps<false, false, 2>);
+    else if (fold) { if (residual) launch(k_gcn_layer_ps<true, false, 0, false, 1>); else launch(k_gcn_layer_ps<true, false, 0, false, 2>); }
     else if (cls) { if (jk) launch(k_gcn_layer_ps<true, true>); else launch(k_gcn_layer_ps<true, false>); }
     else { if (jk) launch(k_gcn_layer_ps<false, true>); else launch(k_gcn_layer_ps<false, false>); }
     g->commit_queue_slice(slot, stream);

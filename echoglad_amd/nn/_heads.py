@@ -106,6 +106,25 @@ def _stack_head_params(params, cfg):
     return P
 
 
+def fold_last_into_heads(weight, scale, shift, w1, s1, t1, residual: bool):
+    """The last GCN layer (no ReLU) folded into the heads' first Linear + eval-mode BatchNorm.  With
+    h3 = scale * ((A_hat h) weight^T) + shift + r h  and  u = s1 * (h3 w1^T) + t1:
+
+        u = (A_hat h) m1^T + r h w1s^T + c1,   m1 = diag(s1) w1 diag(scale) weight,  w1s = diag(s1) w1,  c1 = s1 * (w1 shift) + t1
+
+    scale / shift of None mean 1 and 0.  Computed in float64 on the parameters' device, rounded once -> (m1 [128,128],
+    w1s [128,128], c1 [128]), float32 and contiguous.  ``residual`` enters no value (r multiplies the input in the kernel,
+    eg_gcn_layer_cls_fold_fwd, which skips the second product without it); the argument is there so that the call names
+    everything the launch depends on."""
+    with torch.no_grad():
+        w1d, s1d = w1.double(), s1.double()
+        w = weight.double() if scale is None else scale.double()[:, None] * weight.double()
+        w1s = s1d[:, None] * w1d
+        m1 = w1s @ w
+        c1 = t1.double() if shift is None else s1d * (w1d @ shift.double()) + t1.double()
+        return tuple(t.float().contiguous() for t in (m1, w1s, c1))
+
+
 def _unstack_head_grads(g):
     """eg_classifier_bwd's packed gradients [4 * sum(_HEAD_SIZES)] -> 40 views, one per parameter, in the order of the ``params``
     of _stack_head_params (head k, array j at 10 * k + j)."""

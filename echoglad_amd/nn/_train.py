@@ -31,6 +31,7 @@ class Routes:
     heads_state_in_place = True     # the 4 heads' parameters and running statistics LIVE in the stacked arrays the kernels take (off: copied per step)
     chain_layers = True             # eval: child sums handed from layer to layer (default of HierarchicalPatchModel.chain_layers)
     fuse_classifier = True          # eval: the heads inside the last layer's kernel (default of HierarchicalPatchModel.fuse_classifier)
+    fold_last = True                # eval: ... from the last layer folded into the heads' first Linear (off: the layer's tile is formed in LDS)
 
 
 ROUTES = Routes()

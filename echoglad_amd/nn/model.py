@@ -10,7 +10,7 @@ import torch.nn.functional as F
 
 from .. import ops
 from ..topology import TopologySpec, get_topology
-from ._heads import _HEAD_SIZES, _head_param_offsets, _mlp_kernel_params, _mlp_stats_cfg, _move_into, _seq_params, _views_of
+from ._heads import _HEAD_SIZES, _head_param_offsets, fold_last_into_heads, _mlp_kernel_params, _mlp_stats_cfg, _move_into, _seq_params, _views_of
 from ._resolve import GraphResolver
 from ._train import ROUTES, CoordCfg, HeadsCfg, LayerCfg, Plan, _CoordMlpFn, _TrainFn, _bn_step, new_box
 from .modules import GCNConv, JumpingKnowledge, Sequential, _fold_bn, _versions
@@ -201,6 +201,18 @@ class HierarchicalPatchModel(nn.Module):
             self._fold_cache["cls"] = hit
         return hit[1]
 
+    def _folded_last(self):
+        """(m1, w1s, c1) of _heads.fold_last_into_heads: the last layer (it has no ReLU) inside the heads' first Linear, for
+        eg_gcn_layer_cls_fold_fwd.  Cached on the versions the two tables above are cached on."""
+        key = (tuple(_versions(l) for l in self.gnn_layers), tuple(_versions(c) for c in self.node_classifiers))
+        hit = self._fold_cache.get("fold_last")
+        if hit is None or hit[0] != key:
+            w, scale, shift = self._folded_layers()[-1]
+            packed = self._packed_classifier()
+            hit = (key, fold_last_into_heads(w, scale, shift, packed["w1"], packed["s1"], packed["t1"], bool(self.residual)))
+            self._fold_cache["fold_last"] = hit
+        return hit[1]
+
     # ---- one GNN layer in train mode: one autograd node over eg_gcn_layer_train_fwd / eg_gcn_layer_bwd ------------------
     def _layer_plan(self, i: int, graph: ops.Graph, gb: int, kid=(None, None), boxes=None, counters=None, row_hi: int = 0):
         """(LayerCfg, (weight, bias, gamma, beta)) of layer i for this step -- its dropout seed drawn, its batch counted -- or None
@@ -373,7 +385,12 @@ class HierarchicalPatchModel(nn.Module):
             kid_in, kid_out = self._kid_pair(kids, i)
             jk_prev = None if not jk_fused else (x_in if i == 0 else jkb[(i + 1) & 1])     # max over node features, h_1 .. h_i
             if last and fuse_cls:
-                # the last layer hands its output tile to the classifier heads inside the kernel
+                # the last layer hands its output tile to the classifier heads inside the kernel -- or, without the running
+                # maximum, is part of their first Linear (it has no ReLU) and no such tile is formed
+                if not jk_fused and ROUTES.fold_last:
+                    out = ops.gcn_layer_cls_fold_fwd(graph, gb, x_in, self._folded_last(), bool(self.residual), self._packed_classifier(),
+                                                     sigmoid=sigmoid, kidsum_in=kid_in)
+                    return out.squeeze(1), None
                 out = ops.gcn_layer_cls_fwd(graph, gb, x_in, w, scale, shift, x_in if self.residual else None, False,
                                             self._packed_classifier(), sigmoid=sigmoid, kidsum_in=kid_in, jk_in=jk_prev)
                 return out.squeeze(1), None
@@ -647,7 +664,7 @@ class HierarchicalPatchModel(nn.Module):
             # everything the captured kernels point at stays alive with the entry: the input buffer, the graph handle,
             # the child-sum side buffers and the folded / packed parameters (their caches may evict independently)
             keep = (graph, self._kidsum.get((id(graph), gb)), self._kidsum.get(("jk", id(graph), gb, tuple(node_feats.shape))),
-                    self._fold_cache.get("layers"), self._fold_cache.get("cls"))
+                    self._fold_cache.get("layers"), self._fold_cache.get("cls"), self._fold_cache.get("fold_last"))
             hit = (g, out, node_feats, None, keep)
             self._hip_graphs[key] = hit
         hit[0].replay()

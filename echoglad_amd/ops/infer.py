@@ -74,6 +74,24 @@ def gcn_layer_cls_fwd(graph: Graph, batch: int, x: torch.Tensor, weight: torch.T
     return out
 
 
+def gcn_layer_cls_fold_fwd(graph: Graph, batch: int, x: torch.Tensor, folded, residual: bool, packed: dict, sigmoid: bool = False,
+                           kidsum_in: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gcn_layer_cls_fwd for a last layer without ReLU and without jk_in, from ``folded`` = (m1, w1s, c1) of
+    nn._heads.fold_last_into_heads (the layer's weight, scale and shift and the heads' w1, s1, t1 in one); ``residual``: the
+    layer adds its input.  Same logits to rounding; the layer's output tile is never formed (eg_gcn_layer_cls_fold_fwd)."""
+    rows = graph.num_nodes * batch
+    m1, w1s, c1 = folded
+    _check_rows(x, "x", rows)
+    _check(m1, "m1", (C, C))
+    _check(w1s, "w1s", (C, C))
+    _check(c1, "c1", numel=C)
+    _check_rows(kidsum_in, "kidsum_in", graph.kidsum_rows * batch, optional=True)
+    out = torch.empty((graph.num_nodes - graph.num_conn) * batch, 4, dtype=torch.float32, device=x.device)
+    call("eg_gcn_layer_cls_fold_fwd", graph._h, batch, x, bool(residual), kidsum_in, m1, w1s, c1,
+         *[packed[k] for k in _HEAD_KEYS[3:]], sigmoid, out)
+    return out
+
+
 def new_kidsum(graph: Graph, batch: int) -> Optional[torch.Tensor]:
     """Zero-filled child-sum side buffer [batch * kidsum_rows, 128] for chained layers, or None when the
     topology does not qualify (generic CSR handles, irregular frames)."""

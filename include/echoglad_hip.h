@@ -91,8 +91,9 @@ extern "C" {
  * 143: eg_landmark_record_workspace_bytes, eg_landmark_record_hm, eg_landmark_record_coord.  144: eg_node_labels.
  * 145: eg_conv3x3_relu_bn_fwd, eg_adaptive_max_pool_fwd.
  * 146: eg_frontend_train_workspace_bytes, eg_conv3x3_relu_fwd, eg_bn2d_train_fwd, eg_relu_bn2d_bwd, eg_conv3x3_bwd_data,
- * eg_conv3x3_bwd_weight, eg_adaptive_max_pool_idx_fwd, eg_adaptive_max_pool_bwd.  147: eg_frame_prep. */
-#define EG_ABI_VERSION 147
+ * eg_conv3x3_bwd_weight, eg_adaptive_max_pool_idx_fwd, eg_adaptive_max_pool_bwd.  147: eg_frame_prep.
+ * 148: eg_gcn_layer_cls_fold_fwd. */
+#define EG_ABI_VERSION 148
 
 #define EG_CHANNELS 128 /* node_embedding_dim == node_hidden_dim (configs/default.yml:13-14) */
 
@@ -216,6 +217,17 @@ int eg_gcn_layer_cls_fwd(const eg_graph* g, int batch, const float* x, const flo
                          const float* shift, const float* residual, int relu, const float* kidsum_in, const float* jk_in,
                          const float* w1, const float* s1, const float* t1, const float* w2, const float* s2, const float* t2,
                          const float* w3, const float* b3, int sigmoid, float* logits, eg_stream_t stream);
+/* The same launch for a last layer WITHOUT ReLU (the model's: models.py:431-435 builds it with nn.Identity) and without the
+ * running maximum, from parameters folded once per parameter version: the heads' first pre-activation is linear in the
+ * aggregated rows and the layer's input,
+ *     u = (A_hat x) m1^T + residual * x w1s^T + c1,
+ *     m1 = diag(s1) w1 diag(scale) W [128,128],  w1s = diag(s1) w1 [128,128],  c1 = s1 * (w1 shift) + t1 [128]
+ * (W, scale, shift, w1, s1, t1 as eg_gcn_layer_cls_fwd takes them; echoglad_amd/nn/_heads.py fold_last_into_heads computes the
+ * three in float64).  The layer's output is never formed; logits agree with eg_gcn_layer_cls_fwd to rounding.  residual: 0 or
+ * 1 (the residual is x).  Handles, kidsum_in, w2 .. b3, sigmoid, logits and EG_ERR_UNSUPPORTED as eg_gcn_layer_cls_fwd. */
+int eg_gcn_layer_cls_fold_fwd(const eg_graph* g, int batch, const float* x, int residual, const float* kidsum_in, const float* m1,
+                              const float* w1s, const float* c1, const float* w2, const float* s2, const float* t2, const float* w3,
+                              const float* b3, int sigmoid, float* logits, eg_stream_t stream);
 
 /* JumpingKnowledge('max') of the reference (torch_geometric JumpingKnowledge as used at src/core/models.py:380-382,
  * :479-482: element-wise maximum over [node features, h_1, .., h_L]) carried through the fused stack as a running maximum:
