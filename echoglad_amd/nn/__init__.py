@@ -19,15 +19,17 @@ By role:
     _heads     parameter tables of the heads / coordinate MLPs and their stacked layout
     _train     ROUTES, the train-mode blocks (layer, heads, coordinate update) and the autograd nodes over them
     modules    GCNConv, Sequential, JumpingKnowledge, eval-mode folding
+    embedder   CNNResBlock, CNN: the reference's CNN embedder, torch modules by default, the HIP embedder after enable_hip
     frontend   unet_decoder_maps / unet_decoder_maps_train: the UNet variant's encoder / decoder on the HIP front-end operators
     model      HierarchicalPatchModel: forward_nodes and its three routes"""
 from ._heads import (_HEAD_SIZES, _MLP_NAMES, _head_param_offsets, _mlp_grads, _move_into, _seq_params, _stack_head_params,
                      _unstack_head_grads, _views_of)
 from ._resolve import _SHARED_RESOLVER, GraphResolver
 from ._train import ROUTES, Routes
+from .embedder import CNN, CNNResBlock
 from .frontend import unet_decoder_maps, unet_decoder_maps_train
 from .model import HierarchicalPatchModel
 from .modules import C, GCNConv, JumpingKnowledge, Sequential
 
 __all__ = ["C", "ROUTES", "Routes", "GraphResolver", "HierarchicalPatchModel", "GCNConv", "Sequential", "JumpingKnowledge",
-           "unet_decoder_maps", "unet_decoder_maps_train"]
+           "unet_decoder_maps", "unet_decoder_maps_train", "CNN", "CNNResBlock"]

@@ -92,8 +92,9 @@ extern "C" {
  * 145: eg_conv3x3_relu_bn_fwd, eg_adaptive_max_pool_fwd.
  * 146: eg_frontend_train_workspace_bytes, eg_conv3x3_relu_fwd, eg_bn2d_train_fwd, eg_relu_bn2d_bwd, eg_conv3x3_bwd_data,
  * eg_conv3x3_bwd_weight, eg_adaptive_max_pool_idx_fwd, eg_adaptive_max_pool_bwd.  147: eg_frame_prep.
- * 148: eg_gcn_layer_cls_fold_fwd. */
-#define EG_ABI_VERSION 148
+ * 148: eg_gcn_layer_cls_fold_fwd.
+ * 149: eg_embed_workspace_bytes, eg_embed_block_fwd, eg_embed_conv_fwd, eg_embed_act_fwd, eg_embed_act_bwd, eg_embed_res_bwd_input. */
+#define EG_ABI_VERSION 149
 
 #define EG_CHANNELS 128 /* node_embedding_dim == node_hidden_dim (configs/default.yml:13-14) */
 
@@ -775,6 +776,47 @@ int eg_conv3x3_bwd_weight(const float* x0, int c0, int side0, const float* x1, i
                           void* workspace, float* dweight, eg_stream_t stream);
 int eg_adaptive_max_pool_idx_fwd(const float* x, int planes, int side_in, int side_out, float* out, int* idx, eg_stream_t stream);
 int eg_adaptive_max_pool_bwd(const float* dy, const int* idx, int planes, int side_in, int side_out, float* dx, eg_stream_t stream);
+
+/* ---- CNN embedder (reference: CNNResBlock, src/core/models.py:71-152; the first module of every step) --------------------------
+ * One residual block on x [batch, c_in, side, side], fp32 NCHW, contiguous, square: side 1 .. 512, c_in and c_out 1 .. 128,
+ * batch 1 .. 65535 with batch side^2 < 2^31; 4-byte alignment is enough.
+ *     z = b3 + conv3x3(x, w3, zero padding 1)            w3 [c_out, c_in, 3, 3], b3 [c_out] or NULL: nn.Conv2d's own layout, in place
+ *     y = (z - mean) * gamma / sqrt(var + eps) + beta    the BatchNorm comes BEFORE the ReLU and is not folded into the weights
+ *     r = b1 + w1 x  (1 x 1: w1 [c_out, c_in], b1 [c_out] or NULL)   or   r = x  where w1 == NULL (needs c_in == c_out)
+ *     out = relu(y + r) * keep[b, o]                     (nn.MaxPool2d(1) is the identity; Dropout2d drops whole (b, o) planes)
+ * eg_embed_block_fwd: eval mode, ONE launch: mean / var are the running statistics, keep = 1.  r comes from the centre tap of the
+ *   tile staged for the convolution, so x is read once.  bn_weight, bn_bias may be NULL (1, 0).
+ * Training mode forward, 4 launches:
+ *   eg_embed_conv_fwd:  z (the eval kernel with the plain epilogue);
+ *   eg_bn2d_train_fwd (above) on z: y, save_mean, save_invstd and the running statistics;
+ *   eg_embed_act_fwd:   out = relu(y + r) * keep, and keep [batch * c_out] itself: keep[i] = 0 or 1 / (1 - p), the counter-based mask
+ *     of (seed + this device's dropout epoch, i = b * c_out + o) (csrc/train_common.h keep_scale; eg_dropout_epoch_* move the epoch,
+ *     so replays of a captured step draw fresh planes).  p == 0: keep = 1.
+ * Training mode backward, for g = d out, n = batch side^2, xhat = (z - save_mean) save_invstd:
+ *   eg_embed_act_bwd (3 launches): ds = g keep [out > 0]; dbeta = db1 = sum ds; dgamma = sum ds xhat; dw1[o][c] = sum ds[b, o] x[b, c];
+ *     dz = gamma save_invstd (ds - dbeta / n - xhat dgamma / n); db3 = sum dz (zero but for rounding).  ds, dz [batch, c_out, side,
+ *     side] are required and must not alias an input or each other; dgamma, dbeta, db3, db1 [c_out], dw1 [c_out, c_in] may each be
+ *     NULL (not wanted).  workspace: eg_embed_workspace_bytes(batch, c_in, c_out, side) bytes of device memory (0: shapes out of
+ *     range), owned by the caller.  gamma may be NULL (1).
+ *   eg_conv3x3_bwd_weight / eg_conv3x3_bwd_data (above) on (x, dz) give dw3 and the 3 x 3 part of dx;
+ *   eg_embed_res_bwd_input: dx += w1^T ds (w1 == NULL: dx += ds), in place, AFTER the data gradient.
+ *   5 launches without an input gradient (4 where the weight gradient has one slice), 7 with one.
+ * All: the caller's stream, no allocation, no synchronisation, no atomics; every sum has a fixed order in chains of at most 256
+ * terms (bit-identical from run to run), capturable.  EG_ERR_ARG, nothing launched: a NULL required pointer, batch, a channel count
+ * or side < 1, w1 == NULL with c_in != c_out, b1 without w1, out / z / ds / dz / dx aliasing an input, bn_eps < 0, p outside [0, 1).
+ * EG_ERR_UNSUPPORTED, nothing launched: a channel count above 128, a side above 512, batch above 65535 or batch side^2 >= 2^31. */
+size_t eg_embed_workspace_bytes(int batch, int c_in, int c_out, int side);
+int eg_embed_block_fwd(const float* x, int batch, int c_in, int side, const float* w3, const float* b3, const float* bn_weight,
+                       const float* bn_bias, const float* bn_mean, const float* bn_var, float bn_eps, const float* w1, const float* b1,
+                       int c_out, float* out, eg_stream_t stream);
+int eg_embed_conv_fwd(const float* x, int batch, int c_in, int side, const float* w3, const float* b3, int c_out, float* z,
+                      eg_stream_t stream);
+int eg_embed_act_fwd(const float* y, const float* x, int batch, int c_in, int side, const float* w1, const float* b1, int c_out, float p,
+                     uint64_t seed, float* keep, float* out, eg_stream_t stream);
+int eg_embed_act_bwd(const float* dout, const float* out, const float* keep, const float* x, const float* z, const float* save_mean,
+                     const float* save_invstd, const float* gamma, int batch, int c_in, int c_out, int side, void* workspace, float* ds,
+                     float* dz, float* dgamma, float* dbeta, float* db3, float* db1, float* dw1, eg_stream_t stream);
+int eg_embed_res_bwd_input(const float* ds, const float* w1, int batch, int c_in, int c_out, int side, float* dx, eg_stream_t stream);
 
 /* ---- node-feature packing (the step right before the hot path) -------------------------------------------
  * Reference: the per-sample loops at the tail of create_node_pixels (src/core/models.py:498-537, :590-636,
