@@ -350,8 +350,10 @@ class HierarchicalPatchModel(nn.Module):
         fused = fused and self.layer_output_hook is None and not any(
             p.requires_grad and torch.is_grad_enabled() for p in self.parameters())
         # JumpingKnowledge('max') stays on the fused path as a running maximum written by the layer kernels
-        # (eg_gcn_layer_fwd_jk); where those do not cover the handle (CSR graphs, coordinate / connection nodes) the
-        # layers run one by one and torch takes the maximum, as before
+        # (eg_gcn_layer_fwd_jk); where those do not cover the handle the layers run one by one and torch takes the maximum,
+        # as before: CSR graphs and pyramids without child sums (fused_classifier_ok is False), coordinate nodes, and the
+        # handles with graph.hybrid set -- 'grid-diagonal' levels and connection nodes, which the kernel has no
+        # running-maximum instantiation for (eg_launch_layer_ps refuses them)
         jk_fused = (fused and self.jk is not None and graph.fused_classifier_ok and not self.use_coordinate_graph
                     and not graph.hybrid and ROUTES.jk_fused)
         fused = fused and (self.jk is None or jk_fused)
@@ -373,8 +375,12 @@ class HierarchicalPatchModel(nn.Module):
         # chained layers: each layer leaves the child sums of its output behind for the next one
         if self.chain_layers and not coord and graph.kidsum_rows > 0 and L > 1:
             kids = self._kidsum_buffers(graph, gb)
+        # (a chained stack hands the last layer its child sums; a single layer has no layer in front of it that could, and the
+        #  kernel pulls the child rows itself -- kidsum_in = NULL -- as the first layer of every stack does; graph.hybrid handles
+        #  keep the separate heads there: their fused heads are tested with the child sums handed in only)
         fuse_cls = (self.fuse_classifier and graph.fused_classifier_ok and not coord
-                    and (kids[0] is not None or graph.kidsum_rows == 0) and n_conn == graph.num_conn and n_valid == n - n_conn
+                    and (kids[0] is not None or graph.kidsum_rows == 0 or (L == 1 and self.chain_layers and not graph.hybrid))
+                    and n_conn == graph.num_conn and n_valid == n - n_conn
                     and self.num_output_channels == 4 and self.classifier_hidden_dim == 32)
         jkb = self._jk_buffers(graph, gb, x0) if jk_fused else None
         sigmoid = self.output_activation == "sigmoid"

@@ -56,6 +56,11 @@ static void check_segments(const Topo& T, const TopoTables& tt) {
     for (size_t i = 0; i < tt.segs.size(); ++i) {
         const SegDesc& s = tt.segs[i];
         EXPECT(s.pat >= 0 && s.pat < tt.n_pats, "segment %zu: pat %d of %d", i, s.pat, tt.n_pats);
+        // the consumers' epilogue addresses rows n_first .. n_first + cnt - 1; its running-maximum form reads and writes them through
+        // plain pointers (no buffer descriptor drops a row outside the frame) and repeats segment 0 of the patch for an absent one
+        EXPECT(s.cnt >= 0 && s.cnt <= 8, "segment %zu: cnt %d", i, s.cnt);
+        if (s.cnt > 0) EXPECT(s.n_first >= 0 && s.n_first + s.cnt <= T.n_nodes, "segment %zu: rows %d .. + %d outside the frame", i, s.n_first, s.cnt);
+        if (i % 8 == 0) EXPECT(s.cnt > 0, "patch %zu: segment 0 holds no node", i / 8);
         if (s.mode != 1) continue;
         for (int v : {s.up0, s.down0, s.par0, s.c0, s.c1, s.c2, s.c3}) EXPECT(v >= 0 && v <= hi8, "segment %zu: run base %d outside [0, %d]", i, v, hi8);
         for (int v : {s.left, s.right}) EXPECT(v >= 0 && v <= last, "segment %zu: edge row %d outside [0, %d]", i, v, last);
