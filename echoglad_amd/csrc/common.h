@@ -173,6 +173,8 @@ struct Knobs {
     int stagger;        // EG_STAGGER     experiment: second half of the grid starts late
     int grid_cap;       // EG_GRID        persistent grid of the symmetric kernel (default 512 = 2 workgroups per CU)
     int layer_impl;     // EG_LAYER_IMPL  -1 auto, 0 symmetric kernel, 1 producer/consumer kernel for plain calls
+    int layer_split;    // EG_LAYER_SPLIT 1 (default) the plain eval layer of the producer/consumer kernel multiplies on the bf16 matrix path
+                        //                from exact 3-piece splits (six piece products, fp32-accurate); 0 the chain of fp32 MFMAs
     int ps_grid;        // EG_PS_GRID     persistent grid of the producer/consumer kernel (default 256 = 1 per CU)
     int ring_guard;     // EG_RING_GUARD  0: no event behind a launch (diagnostic: the queue ring is then unguarded, as before round 4)
     int csr_tiles;      // EG_CSR_TILES   CSR handles: 2 (default) clustered 64-node tiles with an LDS row stash, 1 the same stash over

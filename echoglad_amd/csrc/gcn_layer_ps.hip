@@ -140,7 +140,11 @@ __device__ inline void ps_claim(int* __restrict__ counters, int group, int n_til
 // W1s = diag(s1) W1, c = s1 (W1 t) + t1).  FOLD = 1: r = 1, the layer has the residual; FOLD = 2: r = 0, no second product.
 // The caller passes M as W, W1s as ca.w1 and c as ca.t1; the layer's output tile is never formed: no epilogue between the
 // products, no write into s_x, and of s_bn only c is left.
-template <bool CLS, bool JK = false, int MODE = 0, bool DIAG = false, int FOLD = 0>
+// SPLIT (plain eval layer only: !CLS, !JK, MODE 0): the product runs on the bf16 matrix path from exact 3-piece splits of both
+// operands, six piece products per 16-k step (tile.h mfma_rowblock_bf16x6): fp32-accurate, 96 MFMAs of 32 cycles per tile instead
+// of 128 of 64, and beside them the vector datapath stays free for the SIMD's producer wave.  The W slice takes 96 VGPRs instead
+// of 64, so the residual rows are read one 32-row block at a time (RES_LATE, as with the fused heads).
+template <bool CLS, bool JK = false, int MODE = 0, bool DIAG = false, int FOLD = 0, bool SPLIT = false>
 __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __restrict__ x, const float* __restrict__ W,
                                                                 const float* __restrict__ scale, const float* __restrict__ shift,
                                                                 float* __restrict__ out, const float* __restrict__ dis,
@@ -185,6 +189,7 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
         for (int i = tid; i < 4 * TILE * LDA; i += PS_THREADS) smem[i] = 0.f;
     }
     static_assert(!FOLD || (CLS && !JK && MODE == 0), "FOLD is a form of the fused last layer without the running maximum");
+    static_assert(!SPLIT || (!CLS && !JK && MODE == 0), "SPLIT is a form of the plain eval layer");
     if (CLS) {
         if (FOLD) {
             if (tid < C) s_bn[tid] = ca.t1[tid];
@@ -202,7 +207,7 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
     // exactly one workgroup barrier per tile, in lock step:   [prologue barrier]  (tile k work)  [barrier k] ...
     if (wave < 4) {
         // =========================== CONSUMER: channels 32*wave .. 32*wave+31 ===================================
-        constexpr bool RES_LATE = CLS;                 // (the fused-classifier variant has no registers for the residual prefetch)
+        constexpr bool RES_LATE = CLS || SPLIT;        // (the fused-classifier and split variants have no registers for the residual prefetch)
         float wreg[64];
         load_w_slice(W, wave, lane_k, a.transpose_w, wreg);
         // The per-channel scale of the epilogue (eval-mode BatchNorm folded by the caller) goes into the W slice -- lane
@@ -213,6 +218,8 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
 #pragma unroll
             for (int t = 0; t < 64; ++t) wreg[t] *= sv;
         }
+        WPieces wp;                                    // SPLIT: the scaled slice as 3 x 32 VGPRs of bf16 pieces; wreg is dead behind this
+        if constexpr (SPLIT) split_w_slice(wreg, wp);
         f32x16 shv;                                    // !CLS: shift of channel (r & 3) + 8 (r >> 2) + 4 h in register r
         if (!CLS) {
 #pragma unroll
@@ -490,9 +497,15 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
             // (VALU, LDS, and its global stores) is placed between the chunks of the chain, every LDS read one chunk
             // ahead of its use
             auto between = [&](int c) {
-                if (c < 2) { finish_group(acc0, 0, 2 * c); finish_group(acc0, 0, 2 * c + 1); }
+                if (c < 2) {
+                    finish_group(acc0, 0, 2 * c); finish_group(acc0, 0, 2 * c + 1);
+                    if (SPLIT && c == 1) {              // the residual rows of the second block, into the registers the first one has left
+#pragma unroll
+                        for (int g = 0; g < 4; ++g) res[0][g] = *reinterpret_cast<const f32x4*>(s_x + (32 + j) * LDA + 32 * wave + 4 * h + 8 * g);
+                    }
+                }
                 else if (!CLS && c == 2) read_segments(0);
-                else if (!CLS) { store_segments(); if (SUMS) lower_sums(0); kout_half(0); }
+                else if (!CLS) { store_segments(); if (SUMS) lower_sums(0); if (!SPLIT) kout_half(0); }
                 else if (c == 2) {                      // CLS: the residual rows of the second block, into the registers the first one has left
 #pragma unroll
                     for (int g = 0; g < 4; ++g) res[0][g] = *reinterpret_cast<const f32x4*>(s_x + (32 + j) * LDA + 32 * wave + 4 * h + 8 * g);
@@ -514,7 +527,15 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
             asm volatile("" : "+v"(acc1));
             __builtin_amdgcn_sched_barrier(0);
 #else
-            if (!FOLD) {                                   // (FOLD: all four products run as one pipeline, below)
+            if constexpr (SPLIT) {
+                mfma_rowblock_bf16x6(s_a, 0, lane, wp, acc0);
+                mfma_rowblock_bf16x6_with(s_a, 32, lane, wp, acc1, between);
+                // The child sums of rows 0..31 wait for the end of the chain (its last guard: no MFMA of this wave in flight).
+                // Inside a gap of the bf16 chain their packed FMAs left a wrong first component in lanes 48..63 of the stored
+                // row now and then -- the first sighting of the packed-instruction fault this translation unit is built
+                // around (below, in front of ps_split_kernel; DESIGN_NOTES 9.8).  The form measured is the one kept.
+                kout_half(0);
+            } else if (!FOLD) {                            // (FOLD: all four products run as one pipeline, below)
                 mfma_rowblock(s_a, 0, lane, wreg, acc0);
                 mfma_rowblock_with(s_a, 32, lane, wreg, acc1, between);
             }
@@ -978,8 +999,24 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
     }
 }
 
+// The SPLIT instantiations live in a translation unit of their own (gcn_layer_ps_split.hip: this file again, with EG_PS_SPLIT_TU
+// defined), compiled WITHOUT packed fp32 vector instructions (build.py: flag and a check of the object).  Measured on gfx950: a v_pk_fma_f32 / v_pk_mul_f32 that
+// executes on a SIMD beside v_mfma_f32_32x32x16_bf16 -- in the consumer wave itself or in its producer partner -- now and then
+// returns a wrong low result in lanes 48..63 (W = I at (224, 7), batch 8: 56 of 60 launches with rows whose channels 64 + 4 i + 2
+// came back as 0, exactly the low half of the producers' second register pair in those lanes; 0 of 60 without packed
+// instructions).  Beside fp32 MFMAs, which hold the vector datapath, the same instructions never run concurrently, so every
+// other instantiation keeps them (DESIGN_NOTES 9.8).
+using PsKernelFn = decltype(&k_gcn_layer_ps<false>);       // (every instantiation has the same signature; unevaluated: instantiates nothing)
+PsKernelFn ps_split_kernel(bool diag);
+#ifdef EG_PS_SPLIT_TU
+PsKernelFn ps_split_kernel(bool diag) {
+    return diag ? k_gcn_layer_ps<false, false, 0, true, 0, true> : k_gcn_layer_ps<false, false, 0, false, 0, true>;
+}
+#endif
+
 }  // namespace eg
 
+#ifndef EG_PS_SPLIT_TU
 using namespace eg;
 
 int eg_launch_conn_prepass(const eg_graph* g, int batch, const float* x, int slot, hipStream_t stream, const float** base);
@@ -1039,7 +1076,8 @@ int eg_launch_layer_ps(const eg_graph* g, int batch, const float* x, const float
                                      (const void*)k_gcn_layer_ps<false, false, 1, true>, (const void*)k_gcn_layer_ps<false, false, 2, true>,
                                      (const void*)k_gcn_layer_ps<false, false, 3>, (const void*)k_gcn_layer_ps<false, false, 3, true>,
                                      (const void*)k_gcn_layer_ps<true, false, 0, false, 1>, (const void*)k_gcn_layer_ps<true, false, 0, true, 1>,
-                                     (const void*)k_gcn_layer_ps<true, false, 0, false, 2>, (const void*)k_gcn_layer_ps<true, false, 0, true, 2>};
+                                     (const void*)k_gcn_layer_ps<true, false, 0, false, 2>, (const void*)k_gcn_layer_ps<true, false, 0, true, 2>,
+                                     (const void*)ps_split_kernel(false), (const void*)ps_split_kernel(true)};
             for (const void* f : kernels) EG_HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             if (dev >= 0 && dev < 64) attr_set[dev].store(true, std::memory_order_release);
         }
@@ -1087,22 +1125,27 @@ int eg_launch_layer_ps(const eg_graph* g, int batch, const float* x, const float
     };
     if (grid_out) *grid_out = (int)grid;
     eg::LaunchTimer timer(train ? EG_LAUNCH_PS_TRAIN_FWD : rsep ? EG_LAUNCH_PS_DX : cls ? EG_LAUNCH_PS_CLS : EG_LAUNCH_PS_PLAIN, stream);
+    // the plain eval layer takes the split product (exact 3-piece bf16 split, six piece products) unless EG_LAYER_SPLIT=0 asked
+    // for the fp32 chain when the handle was created
+    const bool split = g->knobs.layer_split != 0;
     if (diag) {
         if (train) launch(k_gcn_layer_ps<false, false, 1, true>);
         else if (rsep && lower) launch(k_gcn_layer_ps<false, false, 3, true>);
         else if (rsep) launch(k_gcn_layer_ps<false, false, 2, true>);
         else if (fold) { if (residual) launch(k_gcn_layer_ps<true, false, 0, true, 1>); else launch(k_gcn_layer_ps<true, false, 0, true, 2>); }
         else if (cls) launch(k_gcn_layer_ps<true, false, 0, true>);
+        else if (split) launch(ps_split_kernel(true));
         else launch(k_gcn_layer_ps<false, false, 0, true>);
     } else if (train) launch(k_gcn_layer_ps<false, false, 1>);
     else if (rsep && lower) launch(k_gcn_layer_ps<false, false, 3>);
     else if (rsep) launch(k_gcn_layer_ps<false, false, 2>);
     else if (fold) { if (residual) launch(k_gcn_layer_ps<true, false, 0, false, 1>); else launch(k_gcn_layer_ps<true, false, 0, false, 2>); }
     else if (cls) { if (jk) launch(k_gcn_layer_ps<true, true>); else launch(k_gcn_layer_ps<true, false>); }
-    else { if (jk) launch(k_gcn_layer_ps<false, true>); else launch(k_gcn_layer_ps<false, false>); }
+    else { if (jk) launch(k_gcn_layer_ps<false, true>); else if (split) launch(ps_split_kernel(false)); else launch(k_gcn_layer_ps<false, false>); }
     g->commit_queue_slice(slot, stream);
     g->ps_launches.fetch_add(1u, std::memory_order_relaxed);
     g->layer_launches.fetch_add(1u, std::memory_order_relaxed);
     EG_HIP_TRY(hipGetLastError());
     return EG_OK;
 }
+#endif  // EG_PS_SPLIT_TU

@@ -31,6 +31,7 @@ Knobs read_knobs() {
     // are the defaults and nobody lands on a losing route by accident.
     k.layer_impl = env_int("EG_LAYER_IMPL", -1);
     k.csr_tiles = env_int("EG_CSR_TILES", 2);
+    k.layer_split = env_int("EG_LAYER_SPLIT", 1);
 #ifndef EG_WALK_MODE
 #define EG_WALK_MODE 0
 #endif

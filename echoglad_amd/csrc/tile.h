@@ -558,6 +558,158 @@ __device__ inline void mfma_rowblock_with(const float* s_a, int row0, int lane, 
     EG_CLUMP_FENCE; between(3); EG_CLUMP_FENCE;
 }
 
+// ---- fp32 products on the bf16 matrix path: exact 3-piece split, six piece products ---------------------------------
+// split3: a == hi + mid + lo bit for bit (for |a| >= 2^-110, see below), every piece a float whose low 16 bits are zero (= one
+// bf16 value), all three with a's sign.  Truncation form: hi keeps a's 8 leading significand bits, mid the next 8 of the (exact) remainder a - hi, lo the
+// remainder of that, which has 8 bits left at most.  Both subtractions are exact (Sterbenz-like: the subtrahend is a prefix of
+// the minuend's bits), provided fp32 subnormals are not flushed (they are not: the library is built without
+// -fgpu-flush-denormals-to-zero).
+//   |a| >= 2^-110        exact, also where mid or lo fall below the normal range (< 2^-126): a's last bit is worth 2^-133 or
+//                        more, which is bit 16 of a subnormal's pattern, so the mask cuts nothing off such a remainder.
+//   |a| < 2^-110         (subnormal a and zero included) the mask on a subnormal remainder keeps the bits worth >= 2^-133
+//                        only: |a - (hi + mid + lo)| < 2^-133, the pieces still have a's sign.  -0 gives (-0, +0, +0).
+//   In the kernel a matrix unit that flushes subnormal bf16 inputs drops pieces below 2^-126 on top of that: an absolute
+//   error below 2^-126 |w| per term either way, which is what a flush-to-zero fp32 product gives.
+//   +-inf                hi = +-inf, a - hi = NaN: mid and lo are NaN, the kernel's output row is NaN (the fp32 chain gives
+//                        +-inf or NaN there).
+//   NaN                  hi is NaN, or inf when the payload sits in the low 16 bits only; mid and lo are NaN: NaN out.
+// Non-finite in -> non-finite out in every case; no finite input produces a non-finite piece.
+__host__ __device__ inline float split3_top16(float v) {
+    unsigned u;
+    __builtin_memcpy(&u, &v, 4);
+    u &= 0xFFFF0000u;
+    float r;
+    __builtin_memcpy(&r, &u, 4);
+    return r;
+}
+__host__ __device__ inline void split3(float a, float& hi, float& mid, float& lo) {
+    hi = split3_top16(a);
+    const float r = a - hi;
+    mid = split3_top16(r);
+    lo = split3_top16(r - mid);      // (nothing is cut off: r - mid has at most 8 significant bits)
+}
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+// two pieces (floats with zero low halves) -> one register: element 2i in the low, 2i + 1 in the high 16 bits (one v_perm_b32)
+__device__ inline unsigned pack_top16(float e0, float e1) {
+    return __builtin_amdgcn_perm(__float_as_uint(e1), __float_as_uint(e0), 0x07060302u);
+}
+struct Pieces { bf16x8 hi, mid, lo; };       // 8 consecutive k values of one lane, as MFMA 32x32x16 operands (4 VGPRs each)
+
+__device__ inline Pieces split3_x8(const f32x4& q0, const f32x4& q1) {
+    float hi[8], mid[8], lo[8];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { split3(q0[e], hi[e], mid[e], lo[e]); split3(q1[e], hi[4 + e], mid[4 + e], lo[4 + e]); }
+    u32x4 ph, pm, pl;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        ph[e] = pack_top16(hi[2 * e], hi[2 * e + 1]);
+        pm[e] = pack_top16(mid[2 * e], mid[2 * e + 1]);
+        pl[e] = pack_top16(lo[2 * e], lo[2 * e + 1]);
+    }
+    return Pieces{__builtin_bit_cast(bf16x8, ph), __builtin_bit_cast(bf16x8, pm), __builtin_bit_cast(bf16x8, pl)};
+}
+
+// The W slice of load_w_slice (scaled in fp32 first), split once: step t (k = 64 h + 8 t .. 8 t + 7) in element t of each plane.
+struct WPieces { bf16x8 hi[8], mid[8], lo[8]; };     // 3 x 32 VGPRs
+__device__ inline void split_w_slice(const float (&wreg)[64], WPieces& wp) {
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        const Pieces p = split3_x8(f32x4{wreg[8 * t], wreg[8 * t + 1], wreg[8 * t + 2], wreg[8 * t + 3]},
+                                   f32x4{wreg[8 * t + 4], wreg[8 * t + 5], wreg[8 * t + 6], wreg[8 * t + 7]});
+        wp.hi[t] = p.hi; wp.mid[t] = p.mid; wp.lo[t] = p.lo;
+    }
+}
+
+// DESIGN_NOTES 5.14: v_mfma_f32_32x32x16_bf16 reads its 4-VGPR operands WHILE it executes and nothing interlocks a later VALU
+// write to them.  The rule kept here, literally: the 12 piece registers of a step are complete before the step's first MFMA,
+// stay live (keep_pieces) until the guard behind them, and the guard is a VALU read of the accumulator the step's MFMAs wrote
+// (v_readfirstlane: the compiler adds the XDL-write -> VALU-read wait states, so every MFMA of the step has finished) followed
+// by 16 idle wait states (one s_nop 15; a wait state is 4 cycles, so these are the 64 cycles of 5.14; with 64 wait states the
+// step was slower than the fp32 chain's, DESIGN_NOTES 9.8).  Only behind it may anything write those registers again.  The W
+// pieces are never rewritten.  No test tells a build without this guard from one with it (9.8): it rests on 5.14's count.
+__device__ inline void mfma_operand_guard(const f32x16& acc) {
+    __builtin_amdgcn_sched_barrier(0);
+    const int seen = __builtin_amdgcn_readfirstlane(__float_as_int(acc[0]));
+    asm volatile("" :: "s"(seen));
+#ifndef EG_SPLIT_GUARD_NOPS
+#define EG_SPLIT_GUARD_NOPS 1
+#endif
+#pragma unroll
+    for (int i = 0; i < EG_SPLIT_GUARD_NOPS; ++i) asm volatile("s_nop 15" ::: "memory");      // 16 wait states of 4 cycles each
+    __builtin_amdgcn_sched_barrier(0);
+}
+__device__ inline void keep_pieces(const Pieces& p) {
+    const u32x4 a = __builtin_bit_cast(u32x4, p.hi), b = __builtin_bit_cast(u32x4, p.mid), c = __builtin_bit_cast(u32x4, p.lo);
+    asm volatile("" :: "v"(a.x), "v"(a.y), "v"(a.z), "v"(a.w), "v"(b.x), "v"(b.y), "v"(b.z), "v"(b.w), "v"(c.x), "v"(c.y), "v"(c.z), "v"(c.w));
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+// One 16-k step of one 32-row block: six products in a fixed order, smallest terms first (W piece . A piece).  What is left
+// out -- lo.lo, lo.mid, mid.lo -- is below 2^-24 of |w||a| each.  PART 0: the first product alone; 1: the other five.
+template <int PART>
+__device__ inline void mfma_step_bf16x6(const WPieces& wp, int t, const Pieces& ap, f32x16& acc) {
+    if (PART == 0) {
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wp.lo[t], ap.hi, acc, 0, 0, 0);
+    } else {
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wp.hi[t], ap.lo, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wp.mid[t], ap.mid, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wp.mid[t], ap.hi, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wp.hi[t], ap.mid, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wp.hi[t], ap.hi, acc, 0, 0, 0);
+    }
+}
+
+// The chain of mfma_rowblock on the bf16 path: same LDS operand layout, same f32 fragment reads (lane (j, h) reads
+// a[row0 + j][64 h + s], 16 ds_read_b128), the fragments split in registers.  Two piece sets alternate: while the last five
+// MFMAs of step t run on one set, the VALU splits the fragments of step t + 1 into the other (the bf16 MFMA leaves the vector
+// datapath free, unlike the fp32 one), whose last reader -- step t - 1 -- is behind a guard by then.  between(c), c = 0..3,
+// joins the scheduling region of step 2 c + 1.
+template <typename F>
+__device__ inline void mfma_rowblock_bf16x6_with(const float* s_a, int row0, int lane, const WPieces& wp, f32x16& acc, F between) {
+    const int j = lane & 31, h = lane >> 5;
+    const f32x4* ap = reinterpret_cast<const f32x4*>(s_a + (row0 + j) * LDA + 64 * h);
+    f32x4 raw[2][2];
+    Pieces set[2];
+    raw[0][0] = ap[0]; raw[0][1] = ap[1];
+    raw[1][0] = ap[2]; raw[1][1] = ap[3];
+    set[0] = split3_x8(raw[0][0], raw[0][1]);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        const Pieces& cur = set[t & 1];
+        keep_pieces(cur);                                   // (complete in front of the first MFMA)
+        mfma_step_bf16x6<0>(wp, t, cur, acc);
+        if (t >= 1) {                                       // the other set's last reader, step t - 1, wrote this accumulator too
+            mfma_operand_guard(acc);
+            keep_pieces(set[(t + 1) & 1]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (t < 7) set[(t + 1) & 1] = split3_x8(raw[(t + 1) & 1][0], raw[(t + 1) & 1][1]);
+        if (t < 6) { raw[t & 1][0] = ap[2 * (t + 2)]; raw[t & 1][1] = ap[2 * (t + 2) + 1]; }
+        mfma_step_bf16x6<1>(wp, t, cur, acc);
+        if (t & 1) between(t >> 1);
+        if (t < 7) {
+            // one MFMA, then nine of the split's 44 vector instructions, five times over
+#pragma unroll
+            for (int q = 0; q < 5; ++q) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x002, 9, 0);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    mfma_operand_guard(acc);                                // both sets are free for whoever writes registers next
+    keep_pieces(set[0]);
+    keep_pieces(set[1]);
+}
+
+__device__ inline void mfma_rowblock_bf16x6(const float* s_a, int row0, int lane, const WPieces& wp, f32x16& acc) {
+    mfma_rowblock_bf16x6_with(s_a, row0, lane, wp, acc, [](int) {});
+}
+
 // ---- 8-wave layout: wave w owns 16 output channels, v_mfma_f32_16x16x4_f32 ------------------------
 // A operand = W slice (32 VGPRs for the lifetime of the workgroup): lane (i = l&15, kq = l>>4) holds
 // W[16w+i][koff(kq) + s], s = 0..31.  B operand = LDS tile: lane (j = l&15, kq) reads a[row0+j][koff(kq)+s]

@@ -48,13 +48,15 @@
  *     thread-local error string, and an idempotent per-device "kernel
  *     attribute set" flag.
  *
- *   RUN-TIME ENVIRONMENT VARIABLES -- the complete list (round 6: 7; rounds 3 - 5 had ~20, one per A/B).  Each selects a
+ *   RUN-TIME ENVIRONMENT VARIABLES -- the complete list (8; rounds 3 - 5 had ~20, one per A/B).  Each selects a
  *   FALLBACK route that has to exist anyway (handles, shapes and module states the default route does not cover take it by
  *   themselves); the GPU suite runs under every one of them (tools/knob_matrix.sh).  Everything else that used to be tunable
  *   through the environment is a compile-time constant (-D to experiment) or a Python attribute a test can flip (nn.ROUTES).
  *     library (read once per process / handle, never on a launch path)
  *       EG_LAYER_IMPL=0|1      plain layer calls: 0 the symmetric 8-wave kernel, 1 the producer / consumer kernel (default: by handle)
  *       EG_CSR_TILES=0|1|2     CSR handles: 2 (default) clustered 64-node tiles with an LDS row stash, 1 consecutive rows, 0 row by row
+ *       EG_LAYER_SPLIT=0       plain eval layer of the producer / consumer kernel: the chain of fp32 MFMAs instead of six bf16 products
+ *                              of exact 3-piece splits (same accuracy; the A/B switch and the fallback of that form)
  *       EG_TRAIN_PS=0          training step on the symmetric kernel (what CSR handles take; no handed-down sums)
  *     Python host side (echoglad_amd/, read at the call)
  *       EG_SEQ_FUSED=0         torch_geometric-shaped Sequential: module by module instead of one fused launch per layer
