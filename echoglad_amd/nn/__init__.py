@@ -20,6 +20,8 @@ By role:
     _train     ROUTES, the train-mode blocks (layer, heads, coordinate update) and the autograd nodes over them
     modules    GCNConv, Sequential, JumpingKnowledge, eval-mode folding
     embedder   CNNResBlock, CNN: the reference's CNN embedder, torch modules by default, the HIP embedder after enable_hip
+    cnn_pyramid  CNNHierarchicalPatchModel: the reference's CNN-pyramid variant, torch modules by default, ops.pyramid_block after
+               enable_hip_pyramid
     frontend   unet_decoder_maps / unet_decoder_maps_train: the UNet variant's encoder / decoder on the HIP front-end operators
     model      HierarchicalPatchModel: forward_nodes and its three routes"""
 from ._heads import (_HEAD_SIZES, _MLP_NAMES, _head_param_offsets, _mlp_grads, _move_into, _seq_params, _stack_head_params,
@@ -29,7 +31,8 @@ from ._train import ROUTES, Routes
 from .embedder import CNN, CNNResBlock
 from .frontend import unet_decoder_maps, unet_decoder_maps_train
 from .model import HierarchicalPatchModel
+from .cnn_pyramid import CNNHierarchicalPatchModel
 from .modules import C, GCNConv, JumpingKnowledge, Sequential
 
 __all__ = ["C", "ROUTES", "Routes", "GraphResolver", "HierarchicalPatchModel", "GCNConv", "Sequential", "JumpingKnowledge",
-           "unet_decoder_maps", "unet_decoder_maps_train", "CNN", "CNNResBlock"]
+           "unet_decoder_maps", "unet_decoder_maps_train", "CNN", "CNNResBlock", "CNNHierarchicalPatchModel"]

@@ -1,6 +1,7 @@
 """The CNN embedder's residual block (the reference's CNNResBlock with kernel 3 and pool 1): conv3x3 -> BatchNorm2d -> + residual
 (1 x 1 convolution, or the input itself) -> ReLU -> Dropout2d.  `embed_block` is the eval-mode forward, one launch, inference only;
-`embed_block_train` is the training-mode block with batch statistics, a plane mask and a backward.  Arguments are checked with the
+`embed_block_train` is the training-mode block with batch statistics, a plane mask and a backward; `pyramid_block` is the
+CNN-pyramid variant's eval-mode block (128 -> 128 channels, identity residual, an adaptive max pool behind it).  Arguments are checked with the
 front-end's helpers (`_conv_args`, `_bn_parts`, `_on_device`)."""
 from __future__ import annotations
 
@@ -56,6 +57,30 @@ def embed_block(x: torch.Tensor, conv_w: torch.Tensor, conv_b: Optional[torch.Te
     out = torch.empty((batch, c_out, side, side), dtype=torch.float32, device=x.device)
     call("eg_embed_block_fwd", x.detach(), batch, c_in, side, conv_w.detach(), _det(conv_b), _det(gamma), _det(beta), mean, var, eps,
          _det(one_w), _det(one_b), c_out, out)
+    return out
+
+
+def pyramid_block(x: torch.Tensor, conv_w: torch.Tensor, conv_b: Optional[torch.Tensor], bn, side_out: int) -> torch.Tensor:
+    """relu(AdaptiveMaxPool2d(side_out)(BatchNorm_eval(conv3x3(x) + conv_b) + x)) -> [batch, 128, side_out, side_out]
+    (eg_pyramid_block_fwd): the CNN-pyramid variant's block, 128 -> 128 channels with the input itself as the residual.  The
+    arguments are `embed_block`'s and are checked the same way; 1 <= side_out <= side.  Sides from 4 on run the convolution on the
+    f32-input matrix instruction, smaller ones on `embed_block`'s kernel; the result equals
+    adaptive_max_pool(embed_block(x, conv_w, conv_b, bn), side_out) bit for bit at every side.  Where side_out != side the full-size
+    map goes through a scratch buffer of its own kind ("pyramid": batch * 128 * side^2 floats, grown, never shrunk)."""
+    batch, c_in, c_out, side = _block_args(x, conv_w, conv_b, None, None)
+    if c_in != MAX_CHANNELS or c_out != MAX_CHANNELS:
+        raise RuntimeError(f"the pyramid block covers {MAX_CHANNELS} -> {MAX_CHANNELS} channels, got {c_in} -> {c_out}")
+    side_out = int(side_out)
+    if not 1 <= side_out <= side:
+        raise RuntimeError(f"side_out must be in 1 .. side = {side}, got {side_out}")
+    gamma, beta, mean, var, eps, _, _ = _bn_parts(bn, c_out, training=False)
+    _no_grad_needed("pyramid_block", x, conv_w, conv_b, gamma, beta)
+    _block_on_device(x, conv_w, conv_b, None, None, gamma, beta, mean, var)
+    nbytes = int(raw("eg_pyramid_block_scratch_bytes", batch, side, side_out))
+    scratch = _scratch("pyramid", x.device, nbytes) if nbytes else None
+    out = torch.empty((batch, c_out, side_out, side_out), dtype=torch.float32, device=x.device)
+    call("eg_pyramid_block_fwd", x.detach(), batch, side, conv_w.detach(), _det(conv_b), _det(gamma), _det(beta), mean, var, eps,
+         side_out, scratch, out)
     return out
 
 

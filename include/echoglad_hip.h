@@ -11,6 +11,8 @@
  *   - create_graphs / from_networkx               (src/core/datasets.py:1441-1584, :1392)
  *   - DownConv / UpConv of the UNet front-end, eval (src/core/models.py:841-876: Conv2d 3x3 + ReLU + BatchNorm2d,
  *     nn.Upsample, torch.cat, nn.AdaptiveMaxPool2d)
+ *   - CNNResBlock of the CNN embedder (src/core/models.py:71-152), and of the CNN pyramid in eval mode
+ *     (CNNHierarchicalPatchModel, src/core/models.py:556-636: Conv2d 3x3 128 -> 128 + BatchNorm2d + residual + AdaptiveMaxPool2d + ReLU)
  *
  * Conventions
  *   - every data pointer is a DEVICE pointer, 16-byte aligned, row-major
@@ -95,8 +97,9 @@ extern "C" {
  * 146: eg_frontend_train_workspace_bytes, eg_conv3x3_relu_fwd, eg_bn2d_train_fwd, eg_relu_bn2d_bwd, eg_conv3x3_bwd_data,
  * eg_conv3x3_bwd_weight, eg_adaptive_max_pool_idx_fwd, eg_adaptive_max_pool_bwd.  147: eg_frame_prep.
  * 148: eg_gcn_layer_cls_fold_fwd.
- * 149: eg_embed_workspace_bytes, eg_embed_block_fwd, eg_embed_conv_fwd, eg_embed_act_fwd, eg_embed_act_bwd, eg_embed_res_bwd_input. */
-#define EG_ABI_VERSION 149
+ * 149: eg_embed_workspace_bytes, eg_embed_block_fwd, eg_embed_conv_fwd, eg_embed_act_fwd, eg_embed_act_bwd, eg_embed_res_bwd_input.
+ * 150: eg_pyramid_block_fwd, eg_pyramid_block_scratch_bytes. */
+#define EG_ABI_VERSION 150
 
 #define EG_CHANNELS 128 /* node_embedding_dim == node_hidden_dim (configs/default.yml:13-14) */
 
@@ -819,6 +822,29 @@ int eg_embed_act_bwd(const float* dout, const float* out, const float* keep, con
                      const float* save_invstd, const float* gamma, int batch, int c_in, int c_out, int side, void* workspace, float* ds,
                      float* dz, float* dgamma, float* dbeta, float* db3, float* db1, float* dw1, eg_stream_t stream);
 int eg_embed_res_bwd_input(const float* ds, const float* w1, int batch, int c_in, int c_out, int side, float* dx, eg_stream_t stream);
+
+/* ---- CNN pyramid (reference: CNNHierarchicalPatchModel, src/core/models.py:556-636: seven CNNResBlock(128 -> 128, kernel 3,
+ * AdaptiveMaxPool2d(side_out)) in a row), eval mode -------------------------------------------------------------------------------
+ * eg_pyramid_block_fwd: out [batch, 128, side_out, side_out] = relu(AdaptiveMaxPool2d(side_out)(BatchNorm_eval(conv3x3(x) + b3) + x))
+ *   on x [batch, 128, side, side], fp32 NCHW, contiguous: c_in == c_out == 128, the residual is x itself, zero padding 1.
+ *   w3 [128, 128, 3, 3] is nn.Conv2d's own layout, read in place at every call; b3, bn_weight, bn_bias [128] may be NULL (0, 1, 0) as
+ *   for eg_embed_block_fwd; running_mean, running_var [128].  1 <= side_out <= side <= 512, batch 1 .. 65535 with batch side^2 < 2^31.
+ *   Two steps: the convolution with the epilogue relu(bn(z) + x) (the ReLU in front of the pool: it is monotone, relu(max S) ==
+ *   max relu(S) exactly), written to `scratch` where side_out != side and straight to `out` otherwise; then eg_adaptive_max_pool_fwd
+ *   from scratch to out.  Sides from 4 on run the convolution as an implicit GEMM on the f32-input matrix instruction (the measured
+ *   threshold: it is the faster route at every side of the pyramid), smaller ones on eg_embed_block_fwd's kernel.  THE ORDER OF SUMMATION is fixed and the same on both: k = c * 9 + 3 dy + dx ascending, one
+ *   fmaf chain per output from 0, then + b3 and eg_embed_block_fwd's epilogue -- the result equals eg_embed_block_fwd's (followed by
+ *   the pool) bit for bit at every side.
+ *   scratch: eg_pyramid_block_scratch_bytes(batch, side, side_out) bytes of device memory owned by the caller: batch 128 side^2
+ *   floats, 0 where side_out == side (scratch may then be NULL) or where the shapes are out of range.
+ * The caller's stream, no allocation, no synchronisation, no atomics, bit-identical from run to run, capturable.  EG_ERR_ARG,
+ * nothing launched: a NULL required pointer (scratch where side_out != side), batch or a side < 1, side_out > side, eps < 0, out or
+ * scratch aliasing an input or each other.  EG_ERR_UNSUPPORTED, nothing launched: side above 512, batch above 65535 or
+ * batch side^2 >= 2^31. */
+size_t eg_pyramid_block_scratch_bytes(int batch, int side, int side_out);
+int eg_pyramid_block_fwd(const float* x, int batch, int side, const float* w3, const float* b3, const float* bn_weight,
+                         const float* bn_bias, const float* running_mean, const float* running_var, float eps, int side_out,
+                         float* scratch, float* out, eg_stream_t stream);
 
 /* ---- node-feature packing (the step right before the hot path) -------------------------------------------
  * Reference: the per-sample loops at the tail of create_node_pixels (src/core/models.py:498-537, :590-636,
