@@ -220,6 +220,10 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
         }
         WPieces wp;                                    // SPLIT: the scaled slice as 3 x 32 VGPRs of bf16 pieces; wreg is dead behind this
         if constexpr (SPLIT) split_w_slice(wreg, wp);
+        // The plain eval layer's fp32 chain (EG_LAYER_SPLIT=0) adds the shift behind the chain instead: as the initial value it went
+        // through every rounding of 128 fp32 terms, 12.8 ulp of a result that is mostly shift (tests/test_gpu_eval_fp64.py: 1.17 x
+        // the float64 bound on inputs of 1e-3).  Every other instantiation is as it was.
+        constexpr bool SHIFT_LATE = !CLS && !JK && MODE == 0 && FOLD == 0 && !SPLIT;
         f32x16 shv;                                    // !CLS: shift of channel (r & 3) + 8 (r >> 2) + 4 h in register r
         if (!CLS) {
 #pragma unroll
@@ -375,6 +379,10 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
                     acc0[4 * g] = q.x; acc0[4 * g + 1] = q.y; acc0[4 * g + 2] = q.z; acc0[4 * g + 3] = q.w;
                 }
                 acc1 = acc0;
+            } else if (SHIFT_LATE) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc0[r] = 0.f;
+                acc1 = acc0;
             } else {
                 acc0 = shv;
                 acc1 = shv;
@@ -414,6 +422,7 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
             auto finish_group = [&](const f32x16& acc, int rb, int g) {          // 4 channels of row 32 rb + j -> LDS
                 float* xp = s_x + (32 * rb + j) * LDA + 32 * wave + 4 * h + 8 * g;   // LDS row = 8 * patch row + column
                 f32x4 v = f32x4{acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};          // scale and shift are in already
+                if (SHIFT_LATE) { v.x += shv[4 * g]; v.y += shv[4 * g + 1]; v.z += shv[4 * g + 2]; v.w += shv[4 * g + 3]; }   // (... but for the shift)
                 v.x = max_raw(v.x, relu_floor); v.y = max_raw(v.y, relu_floor); v.z = max_raw(v.z, relu_floor); v.w = max_raw(v.w, relu_floor);
                 if (RES_LATE) {
                     const f32x4 r = res[0][g];

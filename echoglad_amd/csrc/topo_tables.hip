@@ -348,7 +348,10 @@ static bool pair_segments(const Topo& T, const std::vector<TileDesc>& tiles, std
                 topo_debug("kidsum off: parent t=%zu tr=%d level=%d pad0=%d par_raw=%d par0=%d npar=%d kid_rows=%d modes %d %d\n", t, tr, td.level,
                            sa.pad0, par_raw, sa.par0, npar, kid_rows, sa.mode, sb.mode);
             }
-            sa.pad1 = npar;
+            // (par0 is set on the run path alone: a node-by-node segment -- a 'grid-diagonal' level of fewer than 8 columns -- names no
+            //  parents.  With npar it stored sums of rows it never staged at rows par0 = 0 .. of the side buffer, the rows of other
+            //  nodes; its parents run node by node as well and never read theirs, which keep what the caller put there)
+            sa.pad1 = sa.mode == 1 ? npar : 0;
             const bool kids = d.kind == KIND_AUX && ((r >= d.clo && r < d.chi) || (r + 1 >= d.clo && r + 1 < d.chi)) && c0 < d.chi && c0 + 8 > d.clo;
             const bool self_slow = level_diag(T, td.level) && d.side < 8;
             // the pair path reads runs of 8 child-sum rows from each segment's first node: they must stay inside the
