@@ -289,7 +289,6 @@ struct LaunchTimer {
 };
 }  // namespace eg
 
-// producer/consumer layer kernel (gcn_layer_ps.hip); EG_ERR_UNSUPPORTED -> caller uses the symmetric kernel
 namespace eg {
 // Classifier heads fused behind the LAST layer of a stack: node-type filter + 4 x [Linear(128,32)-BN-ReLU-Linear(32,16)-
 // BN-ReLU-Linear(16,1)] of src/core/models.py:363-377, :485-490, eval-mode BN folded by the caller (same packing as
@@ -324,13 +323,28 @@ struct LowerSums {
     float* tile_partial;            // [batch * tiles_per_frame][2][128]
 };
 }  // namespace eg
-// symmetric 8-wave layer kernel (gcn_layer.hip) for any handle; agg_out (nullable) receives the aggregated rows A_hat x,
-// stats_partial (nullable) per-workgroup column sums of out and out^2 as float [*grid_out][2][128]
-int eg_launch_layer_sym(const eg_graph* g, int batch, const float* x, const float* W, const float* scale, const float* shift,
-                        const float* residual, int relu, int transpose_w, float* out, float* agg_out, float* stats_partial,
-                        int* grid_out, hipStream_t stream);
-int eg_launch_layer_ps(const eg_graph* g, int batch, const float* x, const float* W, const float* scale,
-                       const float* shift, const float* residual, int relu, int transpose_w, float* out,
-                       const float* kin, float* kout, const eg::ClsArgs* cls, hipStream_t stream, const float* jk_in = nullptr,
-                       float* jk_out = nullptr, float* agg_out = nullptr, float* stats_partial = nullptr, int* grid_out = nullptr,
-                       const eg::LowerSums* lower = nullptr);
+// One launch of a layer kernel by name: what is left out is NULL / 0.
+namespace eg {
+struct LayerCall {
+    const float* x = nullptr;
+    const float* W = nullptr;
+    const float* scale = nullptr;
+    const float* shift = nullptr;
+    const float* residual = nullptr;
+    int relu = 0, transpose_w = 0;
+    float* out = nullptr;
+    const float* kin = nullptr;         // child sums of x from the layer before / of out for the next one (producer/consumer kernel)
+    float* kout = nullptr;
+    const ClsArgs* cls = nullptr;       // fused heads (producer/consumer kernel)
+    const float* jk_in = nullptr;       // running JumpingKnowledge maximum (producer/consumer kernel)
+    float* jk_out = nullptr;
+    float* agg_out = nullptr;           // train forward: receives the aggregated rows A_hat x ...
+    float* stats_partial = nullptr;     // ... per-workgroup column sums of out and out^2 as float [*grid_out][2][128]
+    int* grid_out = nullptr;
+    const LowerSums* lower = nullptr;   // dX launch of the producer/consumer kernel
+};
+}  // namespace eg
+// symmetric 8-wave layer kernel (gcn_layer.hip) for any handle; reads x .. out, agg_out, stats_partial and grid_out of the call
+int eg_launch_layer_sym(const eg_graph* g, int batch, const eg::LayerCall& call, hipStream_t stream);
+// producer/consumer layer kernel (gcn_layer_ps.hip); EG_ERR_UNSUPPORTED -> caller uses the symmetric kernel
+int eg_launch_layer_ps(const eg_graph* g, int batch, const eg::LayerCall& call, hipStream_t stream);

@@ -351,12 +351,8 @@ __global__ __launch_bounds__(LAYER_THREADS, 4) void k_gcn_layer(const float* __r
         f32x4v acc[4];
 #pragma unroll
         for (int b = 0; b < 4; ++b) acc[b] = f32x4v{0.f, 0.f, 0.f, 0.f};
-#ifndef EG_ABL_NO_MFMA         // timing-only ablation
         mfma16_pair(s_a, 0, lane, wreg, acc[0], acc[1]);
         if (blocks > 2) mfma16_pair(s_a, 32, lane, wreg, acc[2], acc[3]);
-#else
-        acc[0][0] = wreg[lane & 63 ? 1 : 0] + s_a[lane]; acc[1][0] = wreg[31];
-#endif
         // residual rows of this wave's segment (when they are not already in LDS): issued now so their latency
         // hides behind the barriers and the accumulator round trip through LDS.  Paired-row layout: this lane
         // handles rows 2k + h of the segment.  Everything in phase 3 is branch-free: a conditional store becomes
@@ -380,12 +376,8 @@ __global__ __launch_bounds__(LAYER_THREADS, 4) void k_gcn_layer(const float* __r
             const float* rp = (residual ? residual : x) + seg_off;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-#ifndef EG_ABL_NO_P3
                 if (res_stash) res[k] = f32x4{0.f, 0.f, 0.f, 0.f};
                 else res[k] = *reinterpret_cast<const f32x4*>(rp + (long long)rowoff[k] * C);
-#else
-                res[k] = f32x4{0.f, 0.f, 0.f, 0.f};
-#endif
             }
         }
         STAMP(3);
@@ -436,13 +428,7 @@ __global__ __launch_bounds__(LAYER_THREADS, 4) void k_gcn_layer(const float* __r
                 }
             }
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-#ifndef EG_ABL_NO_P3
-                *reinterpret_cast<f32x4*>(op + (long long)rowoff[k] * C) = v[k];
-#else
-                if (v[k].x == 1234.5678f) *reinterpret_cast<f32x4*>(op + (long long)rowoff[k] * C) = v[k];
-#endif
-            }
+            for (int k = 0; k < 4; ++k) *reinterpret_cast<f32x4*>(op + (long long)rowoff[k] * C) = v[k];
         }
         STAMP(7);
         tile = next_tile;
@@ -603,20 +589,18 @@ static int fill_graph_args(const eg_graph* g, int batch, LayerArgs& a, int& agg)
 
 using namespace eg;
 
-int eg_launch_layer_sym(const eg_graph* g, int batch, const float* x, const float* W, const float* scale, const float* shift,
-                        const float* residual, int relu, int transpose_w, float* out, float* agg_out, float* stats_partial,
-                        int* grid_out, hipStream_t stream) {
-    if (!x || !W || !out) return set_error(EG_ERR_ARG, "x, W and out must not be NULL");
-    if (out == x || out == residual || (agg_out && (agg_out == x || agg_out == out)))
+int eg_launch_layer_sym(const eg_graph* g, int batch, const LayerCall& c, hipStream_t stream) {
+    if (!c.x || !c.W || !c.out) return set_error(EG_ERR_ARG, "x, W and out must not be NULL");
+    if (c.out == c.x || c.out == c.residual || (c.agg_out && (c.agg_out == c.x || c.agg_out == c.out)))
         return set_error(EG_ERR_ARG, "out / agg_out must not alias the inputs or each other");
     LayerArgs a{};
     int agg;
     const int rc = fill_graph_args(g, batch, a, agg);
     if (rc != EG_OK) return rc;
-    a.x = x; a.W = W; a.scale = scale; a.shift = shift; a.residual = residual; a.out = out; a.agg_out = agg_out;
-    a.stats_partial = stats_partial;
-    a.d.relu = relu; a.d.transpose_w = transpose_w;
-    return launch_layer(agg, a, stream, grid_out);
+    a.x = c.x; a.W = c.W; a.scale = c.scale; a.shift = c.shift; a.residual = c.residual; a.out = c.out; a.agg_out = c.agg_out;
+    a.stats_partial = c.stats_partial;
+    a.d.relu = c.relu; a.d.transpose_w = c.transpose_w;
+    return launch_layer(agg, a, stream, c.grid_out);
 }
 
 extern "C" {
@@ -638,7 +622,9 @@ int eg_gcn_layer_fwd(const eg_graph* g, int batch, const float* x, const float* 
     int rc = fill_graph_args(g, batch, a, agg);
     if (rc != EG_OK) return rc;
     // implicit topology with the residual in {none, x}: producer/consumer kernel
-    rc = eg_launch_layer_ps(g, batch, x, W, scale, shift, residual, relu, transpose_w, out, nullptr, nullptr, nullptr, (hipStream_t)stream);
+    LayerCall c;
+    c.x = x; c.W = W; c.scale = scale; c.shift = shift; c.residual = residual; c.relu = relu; c.transpose_w = transpose_w; c.out = out;
+    rc = eg_launch_layer_ps(g, batch, c, (hipStream_t)stream);
     if (rc != EG_ERR_UNSUPPORTED) return public_rc(rc);
     a.x = x; a.W = W; a.scale = scale; a.shift = shift; a.residual = residual; a.out = out;
     a.d.relu = relu; a.d.transpose_w = transpose_w;
@@ -653,8 +639,10 @@ int eg_gcn_layer_fwd_chain(const eg_graph* g, int batch, const float* x, const f
     if (kidsum_in && kidsum_in == kidsum_out) return set_error(EG_ERR_ARG, "kidsum_out must not alias kidsum_in");
     if (!kidsum_in && !kidsum_out) return eg_gcn_layer_fwd(g, batch, x, W, scale, shift, residual, relu, transpose_w, out, stream);
     if (!g || batch <= 0) return set_error(EG_ERR_ARG, "bad graph handle or batch");
-    const int rc = eg_launch_layer_ps(g, batch, x, W, scale, shift, residual, relu, transpose_w, out, kidsum_in, kidsum_out,
-                                      nullptr, (hipStream_t)stream);
+    LayerCall c;
+    c.x = x; c.W = W; c.scale = scale; c.shift = shift; c.residual = residual; c.relu = relu; c.transpose_w = transpose_w; c.out = out;
+    c.kin = kidsum_in; c.kout = kidsum_out;
+    const int rc = eg_launch_layer_ps(g, batch, c, (hipStream_t)stream);
     if (rc == EG_ERR_UNSUPPORTED)
         return set_error(EG_ERR_UNSUPPORTED, "chained layers need a topology handle with eg_graph_kidsum_rows() > 0 and residual in {NULL, x}");
     return public_rc(rc);
@@ -676,8 +664,10 @@ int eg_gcn_layer_fwd_jk(const eg_graph* g, int batch, const float* x, const floa
             return set_error(EG_ERR_ARG, "kidsum_in / kidsum_out must not alias x, out, residual, jk_in or jk_out");
     if (kidsum_in && kidsum_in == kidsum_out) return set_error(EG_ERR_ARG, "kidsum_out must not alias kidsum_in");
     if (!g || batch <= 0) return set_error(EG_ERR_ARG, "bad graph handle or batch");
-    const int rc = eg_launch_layer_ps(g, batch, x, W, scale, shift, residual, relu, 0, out, kidsum_in, kidsum_out, nullptr,
-                                      (hipStream_t)stream, jk_in, jk_out);
+    LayerCall c;
+    c.x = x; c.W = W; c.scale = scale; c.shift = shift; c.residual = residual; c.relu = relu; c.out = out;
+    c.kin = kidsum_in; c.kout = kidsum_out; c.jk_in = jk_in; c.jk_out = jk_out;
+    const int rc = eg_launch_layer_ps(g, batch, c, (hipStream_t)stream);
     if (rc == EG_ERR_UNSUPPORTED)
         return set_error(EG_ERR_UNSUPPORTED, "the running JumpingKnowledge maximum needs a topology handle on the producer/consumer kernel "
                                              "(child sums available, or a single-level grid) and residual in {NULL, x}");
@@ -693,9 +683,11 @@ int eg_gcn_layer_cls_fwd(const eg_graph* g, int batch, const float* x, const flo
     if (g->kind != GRAPH_TOPO || g->topo.coord_base < g->n_nodes)
         return set_error(EG_ERR_UNSUPPORTED, "the fused classifier needs a topology handle without coordinate nodes");
     // connection nodes (the first n_conn rows of a frame) are dropped by the heads' node-type filter: logits is [batch * (n - n_conn), 4]
-    eg::ClsArgs c{w1, s1, t1, w2, s2, t2, w3, b3, logits, sigmoid, g->topo.n_conn, (int)g->n_nodes - g->topo.n_conn};
-    const int rc = eg_launch_layer_ps(g, batch, x, W, scale, shift, residual, relu, 0, nullptr, kidsum_in, nullptr, &c,
-                                      (hipStream_t)stream, jk_in, nullptr);
+    const eg::ClsArgs heads{w1, s1, t1, w2, s2, t2, w3, b3, logits, sigmoid, g->topo.n_conn, (int)g->n_nodes - g->topo.n_conn};
+    LayerCall c;
+    c.x = x; c.W = W; c.scale = scale; c.shift = shift; c.residual = residual; c.relu = relu;
+    c.kin = kidsum_in; c.cls = &heads; c.jk_in = jk_in;
+    const int rc = eg_launch_layer_ps(g, batch, c, (hipStream_t)stream);
     if (rc == EG_ERR_UNSUPPORTED)
         return set_error(EG_ERR_UNSUPPORTED, "the fused classifier needs eg_graph_fused_classifier_ok() and residual in {NULL, x}");
     return public_rc(rc);
@@ -708,9 +700,10 @@ int eg_gcn_layer_cls_fold_fwd(const eg_graph* g, int batch, const float* x, int 
     if (!g || batch <= 0) return set_error(EG_ERR_ARG, "bad graph handle or batch");
     if (g->kind != GRAPH_TOPO || g->topo.coord_base < g->n_nodes)
         return set_error(EG_ERR_UNSUPPORTED, "the fused classifier needs a topology handle without coordinate nodes");
-    eg::ClsArgs c{w1s, nullptr, c1, w2, s2, t2, w3, b3, logits, sigmoid, g->topo.n_conn, (int)g->n_nodes - g->topo.n_conn, 1};
-    const int rc = eg_launch_layer_ps(g, batch, x, m1, nullptr, nullptr, residual ? x : nullptr, 0, 0, nullptr, kidsum_in, nullptr, &c,
-                                      (hipStream_t)stream, nullptr, nullptr);
+    const eg::ClsArgs heads{w1s, nullptr, c1, w2, s2, t2, w3, b3, logits, sigmoid, g->topo.n_conn, (int)g->n_nodes - g->topo.n_conn, 1};
+    LayerCall c;
+    c.x = x; c.W = m1; c.residual = residual ? x : nullptr; c.kin = kidsum_in; c.cls = &heads;
+    const int rc = eg_launch_layer_ps(g, batch, c, (hipStream_t)stream);
     if (rc == EG_ERR_UNSUPPORTED)
         return set_error(EG_ERR_UNSUPPORTED, "the fused classifier needs eg_graph_fused_classifier_ok()");
     return public_rc(rc);

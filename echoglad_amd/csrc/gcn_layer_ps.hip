@@ -11,6 +11,7 @@
 // drifting apart.  Tile ids come from the per-XCD queues (tile.h), claimed two tiles ahead by one producer lane.
 #include <stdlib.h>
 
+#include "ps_form.h"
 #include "seg_wide.h"
 #include "train_common.h"
 
@@ -62,33 +63,11 @@ __device__ inline int ps_static_tile(int ord, int n_tiles) {
 #define PSTAMP_FLUSH(base) do {} while (0)
 #endif
 
-// EG_PROBE_SITE / EG_PROBE_N (experiment): N extra vector instructions (v_mov on two scratch registers) at ONE place of the
-// tile loop -- how many cycles does an instruction COST there?  (1 producer: behind the load issue; 2 producer: behind the main
-// stage, in front of the child sums / LDS stores; 3 producer: end of the tile; 4 consumer: top of the tile; 5 consumer: end of
-// the tile, in front of the barrier)
-#ifdef EG_PROBE_SITE
-#ifndef EG_PROBE_N
-#define EG_PROBE_N 64
-#endif
-#define EG_PROBE(site) do { if ((site) == EG_PROBE_SITE) { int pa_ = lane, pb_ = lane; _Pragma("unroll") for (int i_ = 0; i_ < EG_PROBE_N / 2; ++i_) { \
-    asm volatile("v_mov_b32 %0, %0" : "+v"(pa_)); asm volatile("v_mov_b32 %0, %0" : "+v"(pb_)); } asm volatile("" :: "v"(pa_), "v"(pb_)); } } while (0)
-#else
-#define EG_PROBE(site) do {} while (0)
-#endif
-
 // frame = tile / tiles_per_frame (the divisor is loop-invariant: the compiler keeps its reciprocal, a division is ~16 scalar
-// instructions).  EG_FRAME_HINT: try the last frame first (consecutive tiles of a queue mostly lie in one frame).
-__device__ inline int frame_of(int tile, int tiles_per_frame, int& hint) {
-#ifdef EG_FRAME_HINT       // measured (round 4): 16 scalar instructions fewer per role and tile, and 1.3 % SLOWER per step together with the
-                           // branch-free parent-row select below; each of the two alone changes nothing
-    const unsigned t_in = (unsigned)(tile - hint * tiles_per_frame);
-    if (t_in >= (unsigned)tiles_per_frame) hint = tile / tiles_per_frame;
-    return hint;
-#else
-    (void)hint;
-    return tile / tiles_per_frame;
-#endif
-}
+// instructions).  Trying the last frame first (consecutive tiles of a queue mostly lie in one frame) measured 16 scalar instructions
+// fewer per role and tile, and 1.3 % SLOWER per step together with the branch-free parent-row select below; each of the two alone
+// changes nothing (round 4).
+__device__ inline int frame_of(int tile, int tiles_per_frame) { return tile / tiles_per_frame; }
 
 // One v_max_f32.  fmaxf() on a value that comes straight out of an MFMA costs two: the compiler first canonicalises a
 // possible signalling NaN with a v_max_f32 x, x, x of its own.
@@ -278,7 +257,6 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
             lseed = a.lower.seed + epoch_now(a.lower.epoch);
         }
         __syncthreads();                                   // tile 0 is in buffer 0
-        int frame_hint = 0;
         PSTAMP_INIT;
 #ifdef EG_STAMP
         // in-kernel clock (MI355X_MICROARCH.md, DVFS give-back item 6): shader cycles / 100 MHz ticks around the tile loop
@@ -291,15 +269,9 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
             asm volatile("" : "+v"(lane));
             const int cd = s_cd[(k & 1) * 32 + (lane & 31)];
             PSTAMP(3);
-            EG_PROBE(4);
             float* s_a = s_a0 + (k & 1) * TILE * LDA;
             float* s_x = s_x0 + (k & 1) * TILE * LDA;
-#ifdef EG_ABL_HOT          // timing-only ablation: every frame's tiles read and write FRAME 0 (36.9 MB in, as much out: served by L2 / the
-            const int frame = 0;   // memory-side cache, no HBM traffic to speak of); the instruction streams of both roles are unchanged
-            (void)frame_hint;
-#else
-            const int frame = frame_of(t_cur, a.tiles_per_frame, frame_hint);
-#endif
+            const int frame = frame_of(t_cur, a.tiles_per_frame);
             int seg_first[8], seg_cnt[8];
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
@@ -333,14 +305,8 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
                     // the compiler branch on `odd` (two exec-masked paths per select, ~70 instructions per tile)
                     const int npar_e = __builtin_amdgcn_readlane(cd, 4 * (4 * i) + 3), npar_o = __builtin_amdgcn_readlane(cd, 4 * (4 * i + 2) + 3);
                     const int par0_e = __builtin_amdgcn_readlane(cd, 4 * (4 * i) + 2), par0_o = __builtin_amdgcn_readlane(cd, 4 * (4 * i + 2) + 2);
-#ifdef EG_OLD_KOUT_ROW
-                    const int npar = odd ? __builtin_amdgcn_readlane(cd, 4 * (4 * i + 2) + 3) : __builtin_amdgcn_readlane(cd, 4 * (4 * i) + 3);
-                    const int par0 = odd ? __builtin_amdgcn_readlane(cd, 4 * (4 * i + 2) + 2) : __builtin_amdgcn_readlane(cd, 4 * (4 * i) + 2);
-                    (void)npar_e; (void)npar_o; (void)par0_e; (void)par0_o;
-#else
                     const int npar = odd ? npar_o : npar_e;
                     const int par0 = odd ? par0_o : par0_e;
-#endif
                     kout_row[i] = pc < npar ? par0 + pc : -1;
                 }
             }
@@ -501,7 +467,6 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
                 }
                 store_data_guard(o);                   // (the stores' data registers: seg_wide.h)
             };
-#ifndef EG_ABL_NO_MFMA
             // rows 32..63: the MFMA chain leaves ~60 issue cycles per instruction free; the epilogue of rows 0..31
             // (VALU, LDS, and its global stores) is placed between the chunks of the chain, every LDS read one chunk
             // ahead of its use
@@ -520,22 +485,6 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
                     for (int g = 0; g < 4; ++g) res[0][g] = *reinterpret_cast<const f32x4*>(s_x + (32 + j) * LDA + 32 * wave + 4 * h + 8 * g);
                 }
             };
-#if defined(EG_EPI_MID)      // experiment: block 0's whole epilogue as ONE piece between the two chains, chain 2 uninterrupted
-            mfma_rowblock(s_a, 0, lane, wreg, acc0);
-            asm volatile("" : "+v"(acc0));
-            __builtin_amdgcn_sched_barrier(0);
-            if (!CLS) {
-#pragma unroll
-                for (int g = 0; g < 4; ++g) finish_group(acc0, 0, g);
-                read_segments(0); store_segments(); if (SUMS) lower_sums(0); kout_half(0);
-            } else {
-                between(0); between(1); between(2);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            mfma_rowblock(s_a, 32, lane, wreg, acc1);
-            asm volatile("" : "+v"(acc1));
-            __builtin_amdgcn_sched_barrier(0);
-#else
             if constexpr (SPLIT) {
                 mfma_rowblock_bf16x6(s_a, 0, lane, wp, acc0);
                 mfma_rowblock_bf16x6_with(s_a, 32, lane, wp, acc1, between);
@@ -548,26 +497,11 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
                 mfma_rowblock(s_a, 0, lane, wreg, acc0);
                 mfma_rowblock_with(s_a, 32, lane, wreg, acc1, between);
             }
-#endif
-#else
-            acc0[0] += wreg[0] + s_a[lane]; acc1[0] += wreg[63];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) finish_group(acc0, 0, g);
-            if (!CLS) { read_segments(0); store_segments(); if (SUMS) lower_sums(0); kout_half(0); }
-#endif
             PSTAMP(0);
-#ifdef EG_STAMP3                  // finer consumer stamp: the first EG_STAMP3 groups of the exposed epilogue count as "loop"
-#pragma unroll
-            for (int g = 0; g < EG_STAMP3; ++g) finish_group(acc1, 1, g);
-            PSTAMP(3);
-#pragma unroll
-            for (int g = EG_STAMP3; g < 4; ++g) finish_group(acc1, 1, g);
-#else
             if (!FOLD) {
 #pragma unroll
                 for (int g = 0; g < 4; ++g) finish_group(acc1, 1, g);
             }
-#endif
             if (!CLS) {
                 read_segments(4);
                 store_segments();
@@ -761,7 +695,6 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
 #pragma unroll
                 for (int b4 = 0; b4 < 4; ++b4) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(y[b4]), lrsrc, lvoff[b4], 0, 0);
             }
-            EG_PROBE(5);
             PSTAMP(1);
             __syncthreads();                               // barrier k+1: buffer (k+1)&1 is full, buffer k&1 is free
             PSTAMP(2);
@@ -790,16 +723,13 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
     } else {
         // =========================== PRODUCER: patch rows 2p, 2p+1 of every tile ================================
         const int p = wave - 4;
-#ifndef EG_PS_NO_PRIO
         __builtin_amdgcn_s_setprio(3);
-#endif
         PSTAMP_INIT;
         // The two segment descriptors of a tile (32 dwords) travel in ONE VGPR, lane l holding dword l & 31: they are
         // fetched a whole tile ahead (a scalar load at the point of use costs a loaded-memory round trip, ~9k cycles
         // measured, in front of the row loads) and turned into SGPRs with v_readlane when the tile is produced.
-        int desc_hint = 0, prod_hint = 0;
         auto load_desc = [&](int tile_i, int lane) -> int {
-            const int frame = frame_of(tile_i, a.tiles_per_frame, desc_hint);
+            const int frame = frame_of(tile_i, a.tiles_per_frame);
             const int t_in = tile_i - frame * a.tiles_per_frame;
             return reinterpret_cast<const int*>(segs)[(t_in * 8 + 2 * p) * 16 + (lane & 31)];
         };
@@ -816,12 +746,7 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
             return d;
         };
         auto produce = [&](int tile_i, int buf, int lane, int dv) {
-#ifdef EG_ABL_HOT
-            const int frame = 0;
-            (void)prod_hint;
-#else
-            const int frame = frame_of(tile_i, a.tiles_per_frame, prod_hint);
-#endif
+            const int frame = frame_of(tile_i, a.tiles_per_frame);
             const float* __restrict__ xf = x + (size_t)frame * a.n_per_frame * C;
             const SegDesc sd0 = desc_of(dv, 0);
             const SegDesc sd1 = desc_of(dv, 16);
@@ -869,12 +794,8 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
                 // follow once the main stage has freed its registers
                 SegKids K0;
                 if (!RSEP && !DIAG && (sd0.aux & 1) && !use_kin) segw_kids_issue(sd0, pats, xs, lane, K0);      // (RSEP, DIAG: no registers left for them here)
-#ifdef EG_ABL_NO_LOADS        // timing-only ablation: producers do nothing (results wrong)
-                return;
-#endif
                 __builtin_amdgcn_sched_barrier(0);                  // every load of both segments is issued above this line
                 PSTAMP(PS_ISSUE);
-                EG_PROBE(1);
                 const float* wqa = s_pat + sd0.pat * PATQ + 32 * (lane >> 5);      // this lane's weights (LDS, quad layout)
                 const float* wqb = s_pat + sd1.pat * PATQ + 32 * (lane >> 5);
                 float* s_t = (s_x && !RSEP) ? s_x : s_a;            // where the segments' own rows pass through LDS
@@ -908,7 +829,6 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
                 pin_acc4(acc1);                                     // the 40 main-stage registers are dead from here on
                 __builtin_amdgcn_sched_barrier(0);
                 PSTAMP(PS_MAIN);
-                EG_PROBE(2);
                 if (use_kin) {
                     segp_kidsum_add(KS, wqa, wqb, acc0, acc1);
                 } else if (sd0.aux & 1) {                           // uniform: aux level, children pulled as rows
@@ -955,7 +875,6 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
                     }
                 }
             }
-            EG_PROBE(3);
             PSTAMP(2);
         };
         int dv_next = 0;
@@ -1030,67 +949,72 @@ using namespace eg;
 
 int eg_launch_conn_prepass(const eg_graph* g, int batch, const float* x, int slot, hipStream_t stream, const float** base);
 
+// The kernel of a form (ps_form.h PS_FORMS lists the forms; the instantiations are named here and nowhere else).
+static PsKernelFn ps_kernel(const PsForm& f) {
+    if (f.split) return ps_split_kernel(f.diag);
+#define PS_K(CLS, JK, MODE, DIAG, FOLD) {{CLS, JK, MODE, DIAG, FOLD, false}, k_gcn_layer_ps<CLS, JK, MODE, DIAG, FOLD>}
+    static const struct { PsForm form; PsKernelFn fn; } here[] = {      // (the code object holds them in this order)
+        PS_K(false, false, 0, false, 0), PS_K(true, false, 0, false, 0), PS_K(false, true, 0, false, 0), PS_K(true, true, 0, false, 0),
+        PS_K(false, false, 1, false, 0), PS_K(false, false, 2, false, 0),
+        PS_K(false, false, 0, true, 0),  PS_K(true, false, 0, true, 0),  PS_K(false, false, 1, true, 0), PS_K(false, false, 2, true, 0),
+        PS_K(false, false, 3, false, 0), PS_K(false, false, 3, true, 0),
+        PS_K(true, false, 0, false, 1),  PS_K(true, false, 0, true, 1),  PS_K(true, false, 0, false, 2), PS_K(true, false, 0, true, 2),
+    };
+#undef PS_K
+    for (const auto& e : here)
+        if (e.form == f) return e.fn;
+    return nullptr;
+}
+
 // Used by eg_gcn_layer_fwd (gcn_layer.hip) for topology handles when the residual is NULL or x itself.
 // Returns EG_ERR_UNSUPPORTED when the caller should fall back to the symmetric kernel.
-int eg_launch_layer_ps(const eg_graph* g, int batch, const float* x, const float* W, const float* scale,
-                       const float* shift, const float* residual, int relu, int transpose_w, float* out,
-                       const float* kin, float* kout, const eg::ClsArgs* cls, hipStream_t stream, const float* jk_in, float* jk_out,
-                       float* agg_out, float* stats_partial, int* grid_out, const eg::LowerSums* lower) {
-    if (!g || g->kind != GRAPH_TOPO) return EG_ERR_UNSUPPORTED;
-    if (lower && !(residual != nullptr && residual != x)) return set_error(EG_ERR_ARG, "the lower layer's sums go with the dX launch (a residual tensor of its own)");
-    if (lower && (!lower->z || !lower->scale || !lower->shift || !lower->tile_partial || lower->row_hi < 1))
-        return set_error(EG_ERR_ARG, "incomplete LowerSums");
-    const bool train = stats_partial != nullptr;
-    const bool rsep = residual != nullptr && residual != x;       // a residual tensor of its own: MODE 2, plain calls only
-    if (rsep && (train || kin || kout || cls || jk_in || jk_out)) return EG_ERR_UNSUPPORTED;
-    if (agg_out && !train) return set_error(EG_ERR_ARG, "agg_out goes with stats_partial (train forward)");
-    if (train && (kout || cls || jk_in || jk_out)) return set_error(EG_ERR_ARG, "the train forward writes no child sums (its activation pass does) and takes no heads or running maximum");
-    const bool jk = jk_in != nullptr;
-    if ((jk_out != nullptr) != (jk && !cls)) return set_error(EG_ERR_ARG, "jk_out goes with jk_in on a plain layer, the fused heads take jk_in alone");
-    const bool chained = kin || kout || jk;
-    if ((kin || kout) && g->kid_rows == 0) return EG_ERR_UNSUPPORTED;
-    if (jk && g->kid_rows == 0 && !g->flat) return EG_ERR_UNSUPPORTED;
-    if (cls && g->kid_rows == 0 && !g->flat) return EG_ERR_UNSUPPORTED;
-    // plain calls: this kernel by default wherever its fast paths cover the topology -- single-level grids and regular pyramids
-    // (child sums available); since the producers were rebuilt (round 3) its unchained form, which pulls the four child rows of
-    // an aux node, is faster than the symmetric kernel as well (0.280 vs 0.309 ms per launch at configs[1], round 5) -- and the
-    // symmetric kernel on irregular frames; EG_LAYER_IMPL = 0 / 1 forces one of them
-    const bool diag = g->hybrid != 0;                             // 'grid-diagonal' levels: this kernel is the stencil path of such handles
-    if (diag && jk) return EG_ERR_UNSUPPORTED;                    // (the running maximum has no diagonal instantiation: the caller takes it outside)
-    if (!chained && !cls && !train && !rsep && !diag &&
-        (g->knobs.layer_impl < 0 ? (g->flat || g->kid_rows > 0) : g->knobs.layer_impl != 0) == false) return EG_ERR_UNSUPPORTED;
+int eg_launch_layer_ps(const eg_graph* g, int batch, const LayerCall& c, hipStream_t stream) {
+    const bool topo = g && g->kind == GRAPH_TOPO;
+    PsCallFacts cf{};
+    cf.residual = !c.residual ? 0 : c.residual == c.x ? 1 : 2;
+    cf.relu = c.relu != 0; cf.scale = c.scale != nullptr; cf.shift = c.shift != nullptr;
+    cf.kin = c.kin != nullptr; cf.kout = c.kout != nullptr;
+    cf.cls = c.cls != nullptr; cf.fold = c.cls && c.cls->fold;
+    cf.jk_in = c.jk_in != nullptr; cf.jk_out = c.jk_out != nullptr;
+    cf.agg_out = c.agg_out != nullptr; cf.stats_partial = c.stats_partial != nullptr;
+    cf.lower = c.lower != nullptr;
+    cf.lower_complete = c.lower && c.lower->z && c.lower->scale && c.lower->shift && c.lower->tile_partial && c.lower->row_hi >= 1;
+    cf.no_tiles = topo && (long long)g->n_tiles * batch <= 0;
+    PsHandleFacts hf{};
+    hf.topo = topo;
+    if (topo) {
+        hf.hybrid = g->hybrid != 0; hf.flat = g->flat != 0; hf.kids = g->kid_rows > 0;
+        hf.layer_impl = g->knobs.layer_impl; hf.layer_split = g->knobs.layer_split;
+        hf.lds_tables = PS_LDS_PAT + g->n_pats * PATQ;
+    }
+    const PsChoice choice = ps_choose_form(cf, hf);
+    if (choice.rc != EG_OK) return choice.msg ? set_error(choice.rc, choice.msg) : choice.rc;
+    if (!choice.launch) return EG_OK;
+    const PsForm& form = choice.form;
+    const size_t lds = choice.lds;
     PsDims a{};
     a.n_per_frame = (int)g->n_nodes; a.batch = batch; a.tiles_per_frame = g->n_tiles;
-    a.relu = relu; a.transpose_w = transpose_w; a.has_res = residual != nullptr;
+    a.relu = c.relu; a.transpose_w = c.transpose_w; a.has_res = c.residual != nullptr;
     a.kid_rows = g->kid_rows; a.n_pats = g->n_pats;
-    a.agg_out = agg_out; a.stats_partial = stats_partial; a.static_walk = train ? 1 : 0;
-    a.res = rsep ? residual : nullptr;
-    if (lower) a.lower = *lower;
+    a.agg_out = c.agg_out; a.stats_partial = c.stats_partial; a.static_walk = form.mode == 1 ? 1 : 0;
+    a.res = form.mode >= 2 ? c.residual : nullptr;
+    if (c.lower) a.lower = *c.lower;
     const long long n_tiles = (long long)a.tiles_per_frame * batch;
-    if (n_tiles <= 0) return EG_OK;
-    const bool fold = cls && cls->fold;                           // (gcn_layer.hip eg_gcn_layer_cls_fold_fwd: no running maximum, no ReLU)
-    if (fold && (jk || relu || scale || shift)) return set_error(EG_ERR_ARG, "the folded heads take no running maximum, ReLU, scale or shift");
-    // (the folded form keeps one vector in s_bn; topo_tables.hip checks the larger sum)
-    const size_t lds = (size_t)(PS_LDS_PAT + g->n_pats * PATQ + (fold ? C : cls ? 4 * C : 0)) * sizeof(float);
-    if (lds > 160 * 1024) return EG_ERR_UNSUPPORTED;             // more weight patterns than fit beside the tile buffers
     {   // 160 KB of dynamic LDS needs the attribute once per device (idempotent, so a benign race sets it twice at worst)
         static std::atomic<bool> attr_set[64];
         int dev = 0;
         EG_HIP_TRY(hipGetDevice(&dev));
         if (dev < 0 || dev >= 64 || !attr_set[dev].load(std::memory_order_acquire)) {
-            const void* kernels[] = {(const void*)k_gcn_layer_ps<false, false>, (const void*)k_gcn_layer_ps<true, false>,
-                                     (const void*)k_gcn_layer_ps<false, true>, (const void*)k_gcn_layer_ps<true, true>,
-                                     (const void*)k_gcn_layer_ps<false, false, 1>, (const void*)k_gcn_layer_ps<false, false, 2>,
-                                     (const void*)k_gcn_layer_ps<false, false, 0, true>, (const void*)k_gcn_layer_ps<true, false, 0, true>,
-                                     (const void*)k_gcn_layer_ps<false, false, 1, true>, (const void*)k_gcn_layer_ps<false, false, 2, true>,
-                                     (const void*)k_gcn_layer_ps<false, false, 3>, (const void*)k_gcn_layer_ps<false, false, 3, true>,
-                                     (const void*)k_gcn_layer_ps<true, false, 0, false, 1>, (const void*)k_gcn_layer_ps<true, false, 0, true, 1>,
-                                     (const void*)k_gcn_layer_ps<true, false, 0, false, 2>, (const void*)k_gcn_layer_ps<true, false, 0, true, 2>,
-                                     (const void*)ps_split_kernel(false), (const void*)ps_split_kernel(true)};
-            for (const void* f : kernels) EG_HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            for (const PsForm& f : PS_FORMS) {
+                const PsKernelFn fn = ps_kernel(f);
+                if (!fn) return set_error(EG_ERR_HIP, "a form of the layer kernel has no instantiation");
+                EG_HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            }
             if (dev >= 0 && dev < 64) attr_set[dev].store(true, std::memory_order_release);
         }
     }
+    if (!ps_form_listed(form)) return set_error(EG_ERR_HIP, "the layer kernel has no such form");      // (only a listed form has its LDS)
+    const PsKernelFn kernel = ps_kernel(form);
     int* queue = nullptr;
     int slot = -1;
     {
@@ -1117,7 +1041,7 @@ int eg_launch_layer_ps(const eg_graph* g, int batch, const float* x, const float
     a.self_reset = self_reset ? 1 : 0;
     if (g->n_conn > 0) {                                          // connection nodes: level sums of THIS launch's input first (conn.hip)
         const float* slice = nullptr;
-        const int rc = eg_launch_conn_prepass(g, batch, x, slot, stream, &slice);
+        const int rc = eg_launch_conn_prepass(g, batch, c.x, slot, stream, &slice);
         if (rc != EG_OK) return rc;                               // (EG_ERR_UNSUPPORTED: more frames than the scratch holds -> the caller's other kernel)
         a.conn = slice;
         a.conn_stride = (g->conn_chunks + 2 * g->n_conn) * C;
@@ -1127,30 +1051,11 @@ int eg_launch_layer_ps(const eg_graph* g, int batch, const float* x, const float
     }
     long long grid = n_tiles < 256 ? n_tiles : g->knobs.ps_grid;      // one persistent workgroup per CU
     const ClsArgs none{};
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(PS_THREADS), lds, stream, x, W, scale, shift, out, g->dis, g->topo_dev,
-                           g->tiles_dev, g->segs_dev, g->pats_dev, g->patsq_dev, kin, kout, jk_in, jk_out, queue, a, cls ? *cls : none,
-                           (const int*)g->rowptr, (const int*)g->colidx);
-    };
-    if (grid_out) *grid_out = (int)grid;
-    eg::LaunchTimer timer(train ? EG_LAUNCH_PS_TRAIN_FWD : rsep ? EG_LAUNCH_PS_DX : cls ? EG_LAUNCH_PS_CLS : EG_LAUNCH_PS_PLAIN, stream);
-    // the plain eval layer takes the split product (exact 3-piece bf16 split, six piece products) unless EG_LAYER_SPLIT=0 asked
-    // for the fp32 chain when the handle was created
-    const bool split = g->knobs.layer_split != 0;
-    if (diag) {
-        if (train) launch(k_gcn_layer_ps<false, false, 1, true>);
-        else if (rsep && lower) launch(k_gcn_layer_ps<false, false, 3, true>);
-        else if (rsep) launch(k_gcn_layer_ps<false, false, 2, true>);
-        else if (fold) { if (residual) launch(k_gcn_layer_ps<true, false, 0, true, 1>); else launch(k_gcn_layer_ps<true, false, 0, true, 2>); }
-        else if (cls) launch(k_gcn_layer_ps<true, false, 0, true>);
-        else if (split) launch(ps_split_kernel(true));
-        else launch(k_gcn_layer_ps<false, false, 0, true>);
-    } else if (train) launch(k_gcn_layer_ps<false, false, 1>);
-    else if (rsep && lower) launch(k_gcn_layer_ps<false, false, 3>);
-    else if (rsep) launch(k_gcn_layer_ps<false, false, 2>);
-    else if (fold) { if (residual) launch(k_gcn_layer_ps<true, false, 0, false, 1>); else launch(k_gcn_layer_ps<true, false, 0, false, 2>); }
-    else if (cls) { if (jk) launch(k_gcn_layer_ps<true, true>); else launch(k_gcn_layer_ps<true, false>); }
-    else { if (jk) launch(k_gcn_layer_ps<false, true>); else if (split) launch(ps_split_kernel(false)); else launch(k_gcn_layer_ps<false, false>); }
+    if (c.grid_out) *c.grid_out = (int)grid;
+    eg::LaunchTimer timer(form.mode == 1 ? EG_LAUNCH_PS_TRAIN_FWD : form.mode >= 2 ? EG_LAUNCH_PS_DX : form.cls ? EG_LAUNCH_PS_CLS : EG_LAUNCH_PS_PLAIN, stream);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(PS_THREADS), lds, stream, c.x, c.W, c.scale, c.shift, c.out, g->dis, g->topo_dev,
+                       g->tiles_dev, g->segs_dev, g->pats_dev, g->patsq_dev, c.kin, c.kout, c.jk_in, c.jk_out, queue, a, c.cls ? *c.cls : none,
+                       (const int*)g->rowptr, (const int*)g->colidx);
     g->commit_queue_slice(slot, stream);
     g->ps_launches.fetch_add(1u, std::memory_order_relaxed);
     g->layer_launches.fetch_add(1u, std::memory_order_relaxed);

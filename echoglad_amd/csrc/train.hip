@@ -849,12 +849,12 @@ int eg_gcn_layer_train_fwd(const eg_graph* g, int batch, const float* x, const f
     // implicit topologies: the producer / consumer kernel in its train form (static tile walk: bit-reproducible partial sums);
     // anything else, or EG_TRAIN_PS=0: the symmetric kernel
     static const bool train_ps = !(getenv("EG_TRAIN_PS") && atoi(getenv("EG_TRAIN_PS")) == 0);
+    LayerCall c;
+    c.x = x; c.W = W; c.shift = bias; c.out = z; c.kin = kidsum_in; c.agg_out = agg; c.stats_partial = partial; c.grid_out = &grid;
     int rc = EG_ERR_UNSUPPORTED;
-    if (train_ps)
-        rc = eg_launch_layer_ps(g, batch, x, W, nullptr, bias, nullptr, 0, 0, z, kidsum_in, nullptr, nullptr, stream, nullptr, nullptr,
-                                agg, partial, &grid);
-    // (the symmetric kernel pulls the children as rows: it needs no child sums, kidsum_in is simply not used)
-    if (rc == EG_ERR_UNSUPPORTED) rc = eg_launch_layer_sym(g, batch, x, W, nullptr, bias, nullptr, 0, 0, z, agg, partial, &grid, stream);
+    if (train_ps) rc = eg_launch_layer_ps(g, batch, c, stream);
+    // (the symmetric kernel pulls the children as rows: it needs no child sums, kin is simply not used)
+    if (rc == EG_ERR_UNSUPPORTED) rc = eg_launch_layer_sym(g, batch, c, stream);
     if (rc != EG_OK) return public_rc(rc);
     const long long rows = (long long)g->n_nodes * batch;
     BnFinalize f{totals, rows, C, gamma, beta, eps, momentum, running_mean, running_var, bn, bn + C, bn + 2 * C, bn + 3 * C};
@@ -896,13 +896,15 @@ static int gcn_layer_bwd(const eg_graph* g_bwd, int batch, const float* dy, cons
     if (dx) {
         // dX = (A_hat dz) W + dy: the producer / consumer kernel with the residual as a tensor of its own (implicit topologies)
         const bool train_ps = train_ps_on;
+        LayerCall c;
+        c.x = dz_scratch; c.W = W; c.transpose_w = 1; c.residual = dy; c.out = dx;
         rc = EG_ERR_UNSUPPORTED;
         if (lower) {
             const LowerSums ls{lower->z, lower->bn + 2 * C, lower->bn + 3 * C, lower->relu, lower->dropout_p,
                                lower->dropout_p > 0.f ? 1.0f / (1.0f - lower->dropout_p) : 1.0f, (unsigned long long)lower->seed,
                                eg_epoch_ptr(), (int)lower->row_hi, lower->tile_scratch};
-            rc = eg_launch_layer_ps(g_bwd, batch, dz_scratch, W, nullptr, nullptr, dy, 0, 1, dx, nullptr, nullptr, nullptr, stream,
-                                    nullptr, nullptr, nullptr, nullptr, nullptr, &ls);
+            c.lower = &ls;
+            rc = eg_launch_layer_ps(g_bwd, batch, c, stream);
             if (rc == EG_ERR_UNSUPPORTED) return set_error(EG_ERR_HIP, "the dX launch with the lower layer's sums was refused after the layer's own passes had run");
             if (rc != EG_OK) return public_rc(rc);
             const int n_tiles = g_bwd->n_tiles * batch;
@@ -920,10 +922,11 @@ static int gcn_layer_bwd(const eg_graph* g_bwd, int batch, const float* dy, cons
             }
             EG_HIP_TRY(hipGetLastError());
         } else if (train_ps && residual)
-            rc = eg_launch_layer_ps(g_bwd, batch, dz_scratch, W, nullptr, nullptr, dy, 0, 1, dx, nullptr, nullptr, nullptr, stream);
-        if (rc == EG_ERR_UNSUPPORTED && !lower)
-            rc = eg_launch_layer_sym(g_bwd, batch, dz_scratch, W, nullptr, nullptr, residual ? dy : nullptr, 0, 1, dx, nullptr, nullptr,
-                                     nullptr, stream);
+            rc = eg_launch_layer_ps(g_bwd, batch, c, stream);
+        if (rc == EG_ERR_UNSUPPORTED && !lower) {
+            c.residual = residual ? dy : nullptr;
+            rc = eg_launch_layer_sym(g_bwd, batch, c, stream);
+        }
         if (rc != EG_OK) return public_rc(rc);
     }
     // (db = 0 -- a bias in front of a train-mode BatchNorm -- is written by the sums' final kernel: no memset node)
