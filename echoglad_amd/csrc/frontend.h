@@ -46,6 +46,8 @@ __host__ __device__ inline int fe_src(int d, int side0, int side) {
 // shapes every convolution entry point checks the same way; EG_OK or the error that was set
 int fe_check_shapes(int batch, int c0, int c1, int c_out, int side, int side0);
 int fe_launch_conv(const FeConv& A, int mode, hipStream_t stream);
+// out[q] = the sum over S slices of part[s][q], q < Q (frontend_train.hip's k_sum_slices: 8 lane groups x chains of <= 256)
+void fs_launch(const float* part, long long S, int Q, float* out, hipStream_t stream);
 
 // the second source and its channel count come together or not at all; EG_OK or the error that was set
 inline int fe_check_x1(const float* x1, int c1) {

@@ -256,7 +256,7 @@ __global__ __launch_bounds__(FE_THREADS) void k_sum_slices(const float* __restri
     }
 }
 
-static void fs_launch(const float* part, long long S, int Q, float* out, hipStream_t stream) {
+void fs_launch(const float* part, long long S, int Q, float* out, hipStream_t stream) {
     hipLaunchKernelGGL(k_sum_slices, dim3((unsigned)((Q + FS_OUT - 1) / FS_OUT)), dim3(FE_THREADS), 0, stream, part, S, Q, out);
 }
 

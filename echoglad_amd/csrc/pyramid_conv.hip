@@ -21,6 +21,13 @@
 // both routes give the same bits.  9 is odd, so a pair straddles channels ((c, tap 8) with (c + 1, tap 0)); a chunk of 8
 // channels holds 36 whole pairs, and once a chunk is unrolled each lane half's LDS offset is a compile-time constant.
 // No atomics, no allocation, nothing waits for the host; capturable.
+// TRAINING MODE (the order is pool, then ReLU, then dropout, as in the reference) takes the same kernel in two more modes:
+//   PY_PLAIN   eg_pyramid_conv_fwd: z = chain + b3, the chain above, so z equals eg_embed_conv_fwd's bit for bit at every side
+//              (from side 8 on; below, eg_embed_conv_fwd itself: the measured threshold of this epilogue).
+//   PY_DGRAD   eg_pyramid_conv_bwd_data: the B operand is dz, row c of A is the transposed, tap-flipped weight matrix: value
+//              k = o * 9 + tap is w3[o][c][8 - tap] (a thread stages whole nine-float pieces, stride 128 * 9 floats between them,
+//              into the same LDS rows).  The chain is k_conv3x3_tile<., FE_DGRAD>'s: o ascending, tap 0 .. 8 within o, one fmaf
+//              chain from 0; the epilogue adds ds.  From side 17 on: up to 16 eg_conv3x3_bwd_data sums 16 partial chains.
 #include "common.h"
 
 namespace eg {
@@ -28,6 +35,9 @@ namespace eg {
 constexpr int PY_C = EG_CHANNELS;                        // c_in == c_out == 128
 constexpr int PY_MAX_SIDE = 512;
 constexpr int PY_MFMA_MIN_SIDE = 4;                      // below (not measured): the embedder's kernel, the same bits
+constexpr int PY_PLAIN_MFMA_MIN_SIDE = 8;                // the training forward: at side 4 the plain epilogue measured 0.91 - 0.93 x of the
+                                                         // vector kernel (sides 5 - 7 not measured); the bits are the same on both routes
+constexpr int PY_DGRAD_MFMA_MIN_SIDE = 17;               // the data gradient: up to side 16 the existing route is 16 partial chains
 constexpr int PY_THREADS = 256;
 constexpr int PT_W = 32, PT_H = 8;                       // pixel tile of a workgroup
 constexpr int PT_LW = PT_W + 2, PT_LH = PT_H + 2;
@@ -40,10 +50,15 @@ constexpr int PT_WS = PT_K + 1;                          // LDS stride of a weig
 
 typedef float py_f32x16 __attribute__((ext_vector_type(16)));
 
+// what a launch does with a finished chain, and how it reads the weights
+enum { PY_EVAL = 0,         // the eval block: relu(bn(acc + b3) + x)
+       PY_PLAIN = 1,        // the training forward: z = acc + b3
+       PY_DGRAD = 2 };      // the data gradient: x is dz, the weights are read transposed with the taps flipped, dx = acc + ds
+
 struct PyConv {
-    const float* x;         // [batch, 128, side, side]
+    const float* x;         // [batch, 128, side, side]; PY_DGRAD: dz
     const float* w3;        // [128, 128, 3, 3]
-    const float* b3;        // [128] or NULL
+    const float* b3;        // [128] or NULL; PY_DGRAD: ds [batch, 128, side, side] or NULL
     const float* gamma;     // [128] or NULL (1)
     const float* beta;      // [128] or NULL (0)
     const float* mean;      // [128]
@@ -56,7 +71,7 @@ struct PyConv {
 // offset inside the staged chunk of value kk = ci * 9 + 3 dy + dx for the pixel at tile position (0, 0)
 __device__ constexpr int pt_tap(int kk) { return (kk / 9) * PT_POS + ((kk % 9) / 3) * PT_LW + (kk % 9) % 3; }
 
-template <int MA>
+template <int MA, int MODE>
 __global__ __launch_bounds__(PY_THREADS) void k_pyramid_conv(const PyConv A, int tiles_x) {
     constexpr int ROWS = 32 * MA;                        // output channels of the workgroup
     constexpr int TPR = PY_THREADS / ROWS;               // threads that stage one weight row: 2, 4, 8
@@ -81,9 +96,12 @@ __global__ __launch_bounds__(PY_THREADS) void k_pyramid_conv(const PyConv A, int
         const int y = y_lo + ly - 1, x = x_lo + lx - 1;
         off[j] = pos < PT_POS && y >= 0 && y < side && x >= 0 && x < side ? y * side + x : -1;
     }
-    // the weights this thread stages: NW consecutive values of row w_row, from w_k on
+    // the weights this thread stages: NW consecutive values of row w_row, from w_k on.  PY_DGRAD: row c of the transposed matrix,
+    // value kk = o * 9 + tap is w3[o][c][8 - tap]; NW is a multiple of 9 (MA <= 2), so a thread stages whole (o, c) pieces of nine
+    static_assert(MODE != PY_DGRAD || NW % 9 == 0, "the transposed staging takes whole taps");
     const int w_row = t / TPR, w_k = (t - w_row * TPR) * NW;
-    const float* wg = A.w3 + (size_t)(o0 + w_row) * (PY_C * 9) + w_k;
+    const float* wg = MODE == PY_DGRAD ? A.w3 + ((size_t)(w_k / 9) * PY_C + o0 + w_row) * 9
+                                       : A.w3 + (size_t)(o0 + w_row) * (PY_C * 9) + w_k;
     float* wl = s_w + w_row * PT_WS + w_k;
 
     float rin[PT_PER][PT_CIB], rw[NW];
@@ -93,7 +111,8 @@ __global__ __launch_bounds__(PY_THREADS) void k_pyramid_conv(const PyConv A, int
 #pragma unroll
             for (int ci = 0; ci < PT_CIB; ++ci) rin[j][ci] = off[j] >= 0 ? xb[(size_t)(cb + ci) * plane + off[j]] : 0.f;
 #pragma unroll
-        for (int j = 0; j < NW; ++j) rw[j] = wg[cb * 9 + j];
+        for (int j = 0; j < NW; ++j)
+            rw[j] = MODE == PY_DGRAD ? wg[(size_t)(cb + j / 9) * (PY_C * 9) + 8 - j % 9] : wg[cb * 9 + j];
     };
 
     py_f32x16 acc[MA][2];
@@ -144,36 +163,51 @@ __global__ __launch_bounds__(PY_THREADS) void k_pyramid_conv(const PyConv A, int
 #pragma unroll
             for (int j = 0; j < 16; ++j) {
                 const int oc = o0 + a * 32 + (j & 3) + 8 * (j >> 2) + 4 * half;
-                // embedder.hip's epilogue, verbatim (k once for the two rows)
-                const float k = (A.gamma ? A.gamma[oc] : 1.f) / sqrtf(A.var[oc] + A.eps);
-                const float bias = A.b3 ? A.b3[oc] : 0.f, mean = A.mean[oc], beta = A.beta ? A.beta[oc] : 0.f;
+                if (MODE == PY_EVAL) {
+                    // embedder.hip's epilogue, verbatim (k once for the two rows)
+                    const float k = (A.gamma ? A.gamma[oc] : 1.f) / sqrtf(A.var[oc] + A.eps);
+                    const float bias = A.b3 ? A.b3[oc] : 0.f, mean = A.mean[oc], beta = A.beta ? A.beta[oc] : 0.f;
 #pragma unroll
-                for (int r = 0; r < 2; ++r) {
-                    const int y = y_lo + 2 * wave + r;
-                    if (y < side) {
-                        const size_t at = ((size_t)b * PY_C + oc) * plane + y * side + x;
-                        const float res = A.x[at];
-                        const float z = acc[a][r][j] + bias;
-                        const float v = fmaxf((z - mean) * k + beta + res, 0.f);
-                        A.out[at] = v;
+                    for (int r = 0; r < 2; ++r) {
+                        const int y = y_lo + 2 * wave + r;
+                        if (y < side) {
+                            const size_t at = ((size_t)b * PY_C + oc) * plane + y * side + x;
+                            const float res = A.x[at];
+                            const float z = acc[a][r][j] + bias;
+                            const float v = fmaxf((z - mean) * k + beta + res, 0.f);
+                            A.out[at] = v;
+                        }
+                    }
+                } else {
+                    // PY_PLAIN: eg_embed_conv_fwd's z = acc + b3.  PY_DGRAD: the chain, then the residual's share (b3 holds ds)
+                    const float bias = MODE == PY_PLAIN && A.b3 ? A.b3[oc] : 0.f;
+#pragma unroll
+                    for (int r = 0; r < 2; ++r) {
+                        const int y = y_lo + 2 * wave + r;
+                        if (y < side) {
+                            const size_t at = ((size_t)b * PY_C + oc) * plane + y * side + x;
+                            if (MODE == PY_PLAIN) A.out[at] = acc[a][r][j] + bias;
+                            else A.out[at] = A.b3 ? acc[a][r][j] + A.b3[at] : acc[a][r][j];
+                        }
                     }
                 }
             }
     }
 }
 
-template <int MA>
+template <int MA, int MODE>
 static void py_launch(const PyConv& A, int tiles_x, int tiles_y, hipStream_t stream) {
-    hipLaunchKernelGGL((k_pyramid_conv<MA>), dim3(tiles_x * tiles_y, PY_C / (32 * MA), A.batch), dim3(PY_THREADS), 0, stream, A, tiles_x);
+    hipLaunchKernelGGL((k_pyramid_conv<MA, MODE>), dim3(tiles_x * tiles_y, PY_C / (32 * MA), A.batch), dim3(PY_THREADS), 0, stream, A, tiles_x);
 }
 
+template <int MODE>
 static int py_launch_conv(const PyConv& A, hipStream_t stream) {
     const int tiles_x = (A.side + PT_W - 1) / PT_W, tiles_y = (A.side + PT_H - 1) / PT_H;
     // 64 output channels per workgroup halve the staging of the input tile; 32 where that would leave most of the chip without a
     // workgroup (measured at 64, 256 and 1024 tiles: equal from 512 tiles on, 1.5x for 32 channels at 64 tiles: DESIGN 3.6d)
     const long long tiles = (long long)tiles_x * tiles_y * A.batch;
-    if (tiles >= PY_MA1_BELOW) py_launch<2>(A, tiles_x, tiles_y, stream);
-    else py_launch<1>(A, tiles_x, tiles_y, stream);
+    if (tiles >= PY_MA1_BELOW) py_launch<2, MODE>(A, tiles_x, tiles_y, stream);
+    else py_launch<1, MODE>(A, tiles_x, tiles_y, stream);
     EG_HIP_TRY(hipGetLastError());
     return EG_OK;
 }
@@ -211,13 +245,44 @@ int eg_pyramid_block_fwd(const float* x, int batch, int side, const float* w3, c
     float* full = pooled ? scratch : out;
     if (side >= PY_MFMA_MIN_SIDE) {
         const PyConv A{x, w3, b3, bn_weight, bn_bias, running_mean, running_var, full, eps, batch, side};
-        if (const int rc = py_launch_conv(A, (hipStream_t)stream)) return rc;
+        if (const int rc = py_launch_conv<PY_EVAL>(A, (hipStream_t)stream)) return rc;
     } else if (const int rc = eg_embed_block_fwd(x, batch, PY_C, side, w3, b3, bn_weight, bn_bias, running_mean, running_var, eps, nullptr,
                                                  nullptr, PY_C, full, stream)) {
         return rc;
     }
     if (pooled) return eg_adaptive_max_pool_fwd(full, batch * PY_C, side, side_out, out, stream);
     return EG_OK;
+}
+
+// ---- training mode (the pointwise parts, the weight gradient and the workspace are pyramid_train.hip) ----------------------------
+static int py_check_train(int batch, int side) {
+    if (batch < 1) return set_error(EG_ERR_ARG, "batch must be >= 1");
+    if (side < 1) return set_error(EG_ERR_ARG, "side must be >= 1");
+    if (side > PY_MAX_SIDE) return set_error(EG_ERR_UNSUPPORTED, "sides above 512 are not covered");
+    if (batch > 65535 || (long long)batch * side * side >= (1ll << 31)) return set_error(EG_ERR_UNSUPPORTED, "batch too large for one launch");
+    return EG_OK;
+}
+
+int eg_pyramid_conv_fwd(const float* x, int batch, int side, const float* w3, const float* b3, float* z, eg_stream_t stream) {
+    if (!x || !w3 || !z) return set_error(EG_ERR_ARG, "x, w3 and z must not be NULL");
+    if (z == x || z == w3 || (b3 && z == b3)) return set_error(EG_ERR_ARG, "z must not alias an input");
+    if (const int rc = py_check_train(batch, side)) return rc;
+    if (side < PY_PLAIN_MFMA_MIN_SIDE) return eg_embed_conv_fwd(x, batch, PY_C, side, w3, b3, PY_C, z, stream);
+    const PyConv A{x, w3, b3, nullptr, nullptr, nullptr, nullptr, z, 0.f, batch, side};
+    return py_launch_conv<PY_PLAIN>(A, (hipStream_t)stream);
+}
+
+int eg_pyramid_conv_bwd_data(const float* dz, const float* w3, const float* ds, int batch, int side, float* dx, eg_stream_t stream) {
+    if (!dz || !w3 || !dx) return set_error(EG_ERR_ARG, "dz, w3 and dx must not be NULL");
+    if (dx == dz || dx == w3 || (ds && dx == ds)) return set_error(EG_ERR_ARG, "dx must not alias an input");
+    if (const int rc = py_check_train(batch, side)) return rc;
+    if (side < PY_DGRAD_MFMA_MIN_SIDE) {
+        // k_conv3x3_deep adds 16 partial chains per output: one matrix chain would give other bits, so these sides keep the two calls
+        if (const int rc = eg_conv3x3_bwd_data(dz, w3, batch, PY_C, side, PY_C, side, 0, dx, nullptr, nullptr, stream)) return rc;
+        return ds ? eg_embed_res_bwd_input(ds, nullptr, batch, PY_C, PY_C, side, dx, stream) : EG_OK;
+    }
+    const PyConv A{dz, w3, ds, nullptr, nullptr, nullptr, nullptr, dx, 0.f, batch, side};
+    return py_launch_conv<PY_DGRAD>(A, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -7,8 +7,9 @@ level.  Constructor signature, attribute names and state_dict keys are the refer
     conv_hierarchical_grids.{i}.*  the same block objects once more (the reference's IntermediateLayerGetter is a ModuleDict over them)
 
 The default route is the torch modules and runs on the CPU.  `enable_hip_pyramid` switches the blocks to ops.pyramid_block in eval
-mode under torch.no_grad() (csrc/pyramid_conv.hip: the convolution on the f32-input matrix instruction, then the adaptive max pool);
-the tail is the base class's `pack_node_features` (one packing launch) on every route."""
+mode under torch.no_grad() (csrc/pyramid_conv.hip: the convolution on the f32-input matrix instruction, then the adaptive max pool),
+and with ``train=True`` to ops.pyramid_block_train in training mode with autograd on (bit-reproducible, capturable, all three
+convolutions on the matrix instruction, the plane masks drawn from the device's dropout epoch); the tail is the base class's `pack_node_features` (one packing launch) on every route."""
 from __future__ import annotations
 
 from typing import List, Optional
@@ -24,7 +25,7 @@ from .model import C, HierarchicalPatchModel
 def _refuse(where: str, why: str):
     raise NotImplementedError(f"CNNHierarchicalPatchModel.enable_hip_pyramid: {where}: {why} (the HIP pyramid covers Conv2d(128, 128, "
                               "kernel 3, padding 1, stride 1, dilation 1, groups 1, zero padding) -> BatchNorm2d with running "
-                              "statistics -> + input -> AdaptiveMaxPool2d(square) -> ReLU -> Dropout2d on square maps, in eval mode)")
+                              "statistics -> + input -> AdaptiveMaxPool2d(square) -> ReLU -> Dropout2d on square maps)")
 
 
 class CNNHierarchicalPatchModel(HierarchicalPatchModel):
@@ -51,7 +52,8 @@ class CNNHierarchicalPatchModel(HierarchicalPatchModel):
         last = L - 1 if naux > 0 else 0
         self.conv_hierarchical_grids = nn.ModuleDict({str(i): self.conv[i] for i in range(last + 1)})
         self.cnn_layers_out_width = widths
-        self.hip_pyramid = False            # plain attribute: no parameter, no buffer, not in the state_dict
+        self.hip_pyramid = False            # plain attributes: no parameter, no buffer, not in the state_dict
+        self.hip_pyramid_train = False
 
     # ---- the HIP route ---------------------------------------------------------------------------------------------------------
     def _check_block(self, i: int) -> int:
@@ -75,34 +77,57 @@ class CNNHierarchicalPatchModel(HierarchicalPatchModel):
         bn = blk.bn
         if not isinstance(bn, nn.BatchNorm2d) or not bn.track_running_stats or bn.running_mean is None or bn.running_var is None:
             _refuse(f"{where}.bn", "the BatchNorm keeps no running statistics")
+        if bn.momentum is None:
+            _refuse(f"{where}.bn", "the BatchNorm has momentum=None (a cumulative moving average)")
+        if bn.training != self.training:
+            _refuse(f"{where}.bn", f"the BatchNorm is in {'training' if bn.training else 'eval'} mode, the module in "
+                                   f"{'training' if self.training else 'eval'} mode")
         return int(size[0])
 
-    def enable_hip_pyramid(self, flag: bool = True) -> "CNNHierarchicalPatchModel":
+    def enable_hip_pyramid(self, flag: bool = True, train: bool = False) -> "CNNHierarchicalPatchModel":
         """Opt in: in eval mode under torch.no_grad(), with CUDA float32 frames, the blocks run on ops.pyramid_block (one
-        convolution launch on the matrix unit and one pool launch per block, bit-reproducible, capturable).  Training, gradients and
-        CPU tensors stay on the torch modules.  NotImplementedError, naming the block, for a structure the kernel does not cover.
-        Works together with ``enable_hip_graph()``: the packing behind the pyramid writes the static node-feature buffer, so one
-        captured graph serves every batch.  Returns self."""
+        convolution launch on the matrix unit and one pool launch per block, bit-reproducible, capturable).  With train=True also
+        in training mode with autograd on: ops.pyramid_block_train (batch statistics, the plane masks of Dropout2d from a host seed
+        per block plus the device's dropout epoch, a backward with all three convolutions on the matrix unit; the seeds go to
+        ``dropout_seed_hook`` as ("pyramid", block, (seed,))).  Every other combination, and CPU tensors, stay on the torch
+        modules.  NotImplementedError, naming the block, for a structure the kernels do not cover.  Works together with
+        ``enable_hip_graph()``: the packing behind the pyramid writes the static node-feature buffer, so one captured graph serves
+        every batch.  Returns self."""
         if flag:
             for i in range(len(self.conv)):
                 self._check_block(i)
-        self.hip_pyramid = bool(flag)
+        self.hip_pyramid, self.hip_pyramid_train = bool(flag), bool(flag and train)
         return self
 
-    def _hip_route(self, frames: torch.Tensor) -> bool:
-        return (self.hip_pyramid and not self.training and not torch.is_grad_enabled() and frames.is_cuda
-                and frames.dtype == torch.float32)
+    def _hip_route(self, frames: torch.Tensor) -> Optional[str]:
+        if not (frames.is_cuda and frames.dtype == torch.float32):
+            return None
+        if self.hip_pyramid and not self.training and not torch.is_grad_enabled():
+            return "eval"
+        if self.hip_pyramid_train and self.training and torch.is_grad_enabled():
+            return "train"
+        return None
 
     def pyramid_maps(self, frames: torch.Tensor) -> List[torch.Tensor]:
         """[B, 128, F, F] -> the output of every block, in block order (sides cnn_layers_out_width)."""
         outs, x = [], frames
-        if self._hip_route(frames):
+        route = self._hip_route(frames)
+        if route is not None:
             x = x.contiguous()
             for i, blk in enumerate(self.conv):
                 side_out = self._check_block(i)
                 if side_out > x.shape[2]:
                     _refuse(f"conv[{i}].pool", f"output_size {side_out} enlarges the {x.shape[2]} x {x.shape[3]} map")
-                x = E_ops.pyramid_block(x, blk.conv.weight, blk.conv.bias, blk.bn, side_out)
+                if route == "eval":
+                    x = E_ops.pyramid_block(x, blk.conv.weight, blk.conv.bias, blk.bn, side_out)
+                else:
+                    seed = 0
+                    if blk.dropout.p > 0:
+                        # drawn on the host, as nn.CNN draws its seeds; the kernel adds the device's epoch, so a replayed capture moves on
+                        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+                    if self.dropout_seed_hook is not None:
+                        self.dropout_seed_hook("pyramid", i, (seed,))
+                    x = E_ops.pyramid_block_train(x.contiguous(), blk.conv.weight, blk.conv.bias, blk.bn, side_out, blk.dropout.p, seed)
                 outs.append(x)
             return outs
         for blk in self.conv:

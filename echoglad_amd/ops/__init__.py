@@ -19,7 +19,7 @@ from .criteria import (CONFUSION_MAX_CHANNELS, CONFUSION_WORKSPACE_BYTES, LANDMA
                        heatmap_expect_bwd, heatmap_expect_fwd, landmark_criteria, landmark_record_coord, landmark_record_hm,
                        landmark_record_workspace_bytes)
 from .frontend import adaptive_max_pool, adaptive_max_pool_train, conv3x3_relu_bn, conv3x3_relu_bn_train               # noqa: F401
-from .embedder import embed_block, embed_block_train, pyramid_block                                                             # noqa: F401
+from .embedder import embed_block, embed_block_train, pyramid_block, pyramid_block_train                                        # noqa: F401
 from .frame_prep import frame_prep                                                                                     # noqa: F401
 from .labels import node_labels                                                                                  # noqa: F401
 from .pack import avg_pool_pyramid, conv1x1_relu_pack_levels, pack_levels, pyramid_pack, pyramid_supported             # noqa: F401

@@ -1,7 +1,8 @@
 """The CNN embedder's residual block (the reference's CNNResBlock with kernel 3 and pool 1): conv3x3 -> BatchNorm2d -> + residual
 (1 x 1 convolution, or the input itself) -> ReLU -> Dropout2d.  `embed_block` is the eval-mode forward, one launch, inference only;
 `embed_block_train` is the training-mode block with batch statistics, a plane mask and a backward; `pyramid_block` is the
-CNN-pyramid variant's eval-mode block (128 -> 128 channels, identity residual, an adaptive max pool behind it).  Arguments are checked with the
+CNN-pyramid variant's eval-mode block (128 -> 128 channels, identity residual, an adaptive max pool behind it) and
+`pyramid_block_train` that block in training mode with its backward.  Arguments are checked with the
 front-end's helpers (`_conv_args`, `_bn_parts`, `_on_device`)."""
 from __future__ import annotations
 
@@ -67,12 +68,8 @@ def pyramid_block(x: torch.Tensor, conv_w: torch.Tensor, conv_b: Optional[torch.
     f32-input matrix instruction, smaller ones on `embed_block`'s kernel; the result equals
     adaptive_max_pool(embed_block(x, conv_w, conv_b, bn), side_out) bit for bit at every side.  Where side_out != side the full-size
     map goes through a scratch buffer of its own kind ("pyramid": batch * 128 * side^2 floats, grown, never shrunk)."""
-    batch, c_in, c_out, side = _block_args(x, conv_w, conv_b, None, None)
-    if c_in != MAX_CHANNELS or c_out != MAX_CHANNELS:
-        raise RuntimeError(f"the pyramid block covers {MAX_CHANNELS} -> {MAX_CHANNELS} channels, got {c_in} -> {c_out}")
-    side_out = int(side_out)
-    if not 1 <= side_out <= side:
-        raise RuntimeError(f"side_out must be in 1 .. side = {side}, got {side_out}")
+    batch, side, side_out = _pyramid_args(x, conv_w, conv_b, side_out)
+    c_out = MAX_CHANNELS
     gamma, beta, mean, var, eps, _, _ = _bn_parts(bn, c_out, training=False)
     _no_grad_needed("pyramid_block", x, conv_w, conv_b, gamma, beta)
     _block_on_device(x, conv_w, conv_b, None, None, gamma, beta, mean, var)
@@ -82,6 +79,95 @@ def pyramid_block(x: torch.Tensor, conv_w: torch.Tensor, conv_b: Optional[torch.
     call("eg_pyramid_block_fwd", x.detach(), batch, side, conv_w.detach(), _det(conv_b), _det(gamma), _det(beta), mean, var, eps,
          side_out, scratch, out)
     return out
+
+
+def _pyramid_args(x, conv_w, conv_b, side_out):
+    """The checks both pyramid blocks make -> (batch, side, side_out)."""
+    batch, c_in, c_out, side = _block_args(x, conv_w, conv_b, None, None)
+    if c_in != MAX_CHANNELS or c_out != MAX_CHANNELS:
+        raise RuntimeError(f"the pyramid block covers {MAX_CHANNELS} -> {MAX_CHANNELS} channels, got {c_in} -> {c_out}")
+    side_out = int(side_out)
+    if not 1 <= side_out <= side:
+        raise RuntimeError(f"side_out must be in 1 .. side = {side}, got {side_out}")
+    return batch, side, side_out
+
+
+def _pyramid_workspace(device, batch: int, side: int, side_out: int) -> torch.Tensor:
+    """One workspace for a training-mode pyramid block (eg_pyramid_train_workspace_bytes): the chunk sums of the BatchNorm in both
+    directions and the weight gradient's slices, at most 64 of them whatever the batch and the side."""
+    return _scratch("pyramid_train", device, max(int(raw("eg_pyramid_train_workspace_bytes", batch, side, side_out)), 256))
+
+
+class _PyramidBlockTrain(torch.autograd.Function):
+    """Saved: x, z, idx and out (pooled), keep, the batch mean and 1 / std, and references to the parameters -- never y, never
+    v = y + x or any other full-size map."""
+
+    @staticmethod
+    def forward(ctx, x, conv_w, conv_b, gamma, beta, stats, eps, momentum, side_out, p, seed):
+        batch, side, dev, C = int(x.shape[0]), int(x.shape[2]), x.device, MAX_CHANNELS
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        z, y, out = new(batch, C, side, side), new(batch, C, side, side), new(batch, C, side_out, side_out)
+        idx = torch.empty((batch, C, side_out, side_out), dtype=torch.int32, device=dev)
+        save_mean, save_invstd, keep = new(C), new(C), new(batch * C)
+        call("eg_pyramid_conv_fwd", x.detach(), batch, side, conv_w.detach(), _det(conv_b), z)
+        call("eg_bn2d_train_fwd", z, batch, C, side, _det(gamma), _det(beta), eps, momentum, stats[0], stats[1],
+             _pyramid_workspace(dev, batch, side, side_out), y, save_mean, save_invstd)
+        call("eg_pyramid_act_fwd", y, x.detach(), batch, side, side_out, p, seed, keep, idx, out)
+        ctx.save_for_backward(x, conv_w, gamma, out, z, idx, keep, save_mean, save_invstd)
+        ctx.has = (conv_b is not None, beta is not None)
+        ctx.mark_non_differentiable(keep)
+        return out, keep
+
+    @staticmethod
+    @once_differentiable                    # a double backward raises
+    def backward(ctx, dout, _dkeep):
+        x, conv_w, gamma, out, z, idx, keep, save_mean, save_invstd = ctx.saved_tensors
+        need_x, need_w3, need_b3, need_g, need_be = ctx.needs_input_grad[:5]
+        has_b3, has_beta = ctx.has
+        batch, side, side_out, dev, C = int(x.shape[0]), int(x.shape[2]), int(out.shape[2]), x.device, MAX_CHANNELS
+        dout = dout.contiguous()
+        if dout.dtype != torch.float32 or dout.shape != out.shape:
+            raise RuntimeError(f"pyramid_block_train backward: dout must be float32 {tuple(out.shape)}, got {dout.dtype} {tuple(dout.shape)}")
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        ds, dz = torch.empty_like(z), torch.empty_like(z)
+        dgamma = new(C) if need_g and gamma is not None else None
+        dbeta = new(C) if need_be and has_beta else None
+        db3 = new(C) if need_b3 and has_b3 else None
+        ws = _pyramid_workspace(dev, batch, side, side_out)
+        call("eg_pyramid_act_bwd", dout, out, keep, idx, z, save_mean, save_invstd, gamma, batch, side, side_out, ws, ds, dz, dgamma,
+             dbeta, db3)
+        dw3 = dx = None
+        if need_w3:
+            dw3 = torch.empty_like(conv_w)
+            call("eg_pyramid_conv_bwd_weight", x, dz, batch, side, ws, dw3)
+        if need_x:                          # the chain, then the residual's share in the epilogue: always this order
+            dx = torch.empty_like(x)
+            call("eg_pyramid_conv_bwd_data", dz, conv_w, ds, batch, side, dx)
+        return dx, dw3, db3, dgamma, dbeta, None, None, None, None, None, None
+
+
+def pyramid_block_train(x: torch.Tensor, conv_w: torch.Tensor, conv_b: Optional[torch.Tensor], bn, side_out: int, p: float, seed: int,
+                        return_keep: bool = False):
+    """Dropout2d_p(relu(AdaptiveMaxPool2d(side_out)(BatchNorm_train(conv3x3(x) + conv_b) + x))) -> [batch, 128, side_out, side_out],
+    with a backward (gradients of x, conv_w, conv_b and the BatchNorm's weight and bias, each only where it is asked for): the
+    CNN-pyramid block in training mode, pool, then ReLU, then dropout as in the reference.  The arguments are `pyramid_block`'s and
+    are checked the same way; bn is an nn.BatchNorm2d in TRAINING mode -- its running statistics and num_batches_tracked move as
+    nn.BatchNorm2d moves them -- or (weight, bias, running_mean | None, running_var | None, eps, momentum).  The plane mask is
+    `embed_block_train`'s (seed + the device's dropout epoch, b * 128 + o); return_keep: also return it [batch * 128].  All three
+    convolutions run on the f32-input matrix instruction (the data gradient from side 17 on); the weight gradient's workspace is at
+    most 64 slices whatever the batch and the side (scratch kind "pyramid_train").  Bit-reproducible, capturable; CUDA tensors only."""
+    batch, side, side_out = _pyramid_args(x, conv_w, conv_b, side_out)
+    gamma, beta, mean, var, eps, momentum, module = _bn_parts(bn, MAX_CHANNELS, training=True)
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dropout probability has to be in [0, 1), but got {p}")
+    if batch * side * side == 1:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {(batch, MAX_CHANNELS, side, side)}")
+    _block_on_device(x, conv_w, conv_b, None, None, gamma, beta, mean, var)
+    out, keep = _PyramidBlockTrain.apply(x, conv_w, conv_b, gamma, beta, (mean, var), eps, momentum, side_out, p, _seed(seed))
+    if module is not None and module.num_batches_tracked is not None:
+        module.num_batches_tracked.add_(1)
+    return (out, keep) if return_keep else out
 
 
 def _workspace(device, batch: int, c_in: int, c_out: int, side: int) -> torch.Tensor:

@@ -98,8 +98,10 @@ extern "C" {
  * eg_conv3x3_bwd_weight, eg_adaptive_max_pool_idx_fwd, eg_adaptive_max_pool_bwd.  147: eg_frame_prep.
  * 148: eg_gcn_layer_cls_fold_fwd.
  * 149: eg_embed_workspace_bytes, eg_embed_block_fwd, eg_embed_conv_fwd, eg_embed_act_fwd, eg_embed_act_bwd, eg_embed_res_bwd_input.
- * 150: eg_pyramid_block_fwd, eg_pyramid_block_scratch_bytes. */
-#define EG_ABI_VERSION 150
+ * 150: eg_pyramid_block_fwd, eg_pyramid_block_scratch_bytes.
+ * 151: eg_pyramid_train_workspace_bytes, eg_pyramid_conv_fwd, eg_pyramid_act_fwd, eg_pyramid_act_bwd, eg_pyramid_conv_bwd_data,
+ * eg_pyramid_conv_bwd_weight. */
+#define EG_ABI_VERSION 151
 
 #define EG_CHANNELS 128 /* node_embedding_dim == node_hidden_dim (configs/default.yml:13-14) */
 
@@ -845,6 +847,51 @@ size_t eg_pyramid_block_scratch_bytes(int batch, int side, int side_out);
 int eg_pyramid_block_fwd(const float* x, int batch, int side, const float* w3, const float* b3, const float* bn_weight,
                          const float* bn_bias, const float* running_mean, const float* running_var, float eps, int side_out,
                          float* scratch, float* out, eg_stream_t stream);
+
+/* ---- CNN pyramid, training mode (the same block with batch statistics, a pool with indices, a plane mask, and its backward) ----
+ * x [batch, 128, side, side], fp32 NCHW, contiguous; 1 <= side_out <= side <= 512, batch 1 .. 65535 with batch side^2 < 2^31.
+ * THE ORDER IS POOL, THEN ReLU, THEN DROPOUT, as in the reference's CNNResBlock.forward:
+ *     z = b3 + conv3x3(x, w3, zero padding 1)            w3 [128, 128, 3, 3] read in place, b3 [128] or NULL
+ *     y = (z - mean) * gamma / sqrt(var + eps) + beta    eg_bn2d_train_fwd (above) on z, unchanged: batch statistics, running ones move
+ *     v = y + x                                          full size, never written
+ *     (m, idx) = AdaptiveMaxPool2d(side_out)(v)          idx: the first maximum of a window in row-major order, a NaN takes over
+ *     out = relu(m) * keep[b, o]                         keep: eg_embed_act_fwd's plane mask (seed + the device's epoch; p == 0: 1)
+ * Backward, for g = d out, n = batch side^2, xhat = (z - save_mean) save_invstd:
+ *     gp = g keep [out > 0] (pooled);  ds = the pool's backward of gp through idx: every input pixel adds the windows whose idx it is,
+ *     in window order;  dbeta = sum ds, dgamma = sum ds xhat;  dz = gamma save_invstd (ds - dbeta / n - xhat dgamma / n);  db3 = sum dz;
+ *     dw3 = the weight gradient of (x, dz);  dx = the data gradient of (dz, w3) + ds, the residual's share added AFTER the chain.
+ * eg_pyramid_conv_fwd: z.  The eval kernel with the plain epilogue from side 8 on (the measured threshold of this epilogue),
+ *     eg_embed_conv_fwd below: the same summation order (k = c * 9 + tap ascending, one fmaf chain from 0, + b3), so z equals
+ *     eg_embed_conv_fwd's bit for bit at every side.
+ * eg_pyramid_act_fwd: keep [batch * 128], idx and out [batch, 128, side_out, side_out] from y and x, one launch.  With p == 0, out
+ *     equals eg_adaptive_max_pool_idx_fwd of eg_embed_act_fwd's out bit for bit, and idx equals that pool's wherever out > 0 (where
+ *     out == 0 the pool of the rectified map picks the first zero, this one v's largest negative).
+ * eg_pyramid_act_bwd (2 launches, 3 with db3): ds, dz [batch, 128, side, side], required, not aliasing an input or each other; dgamma,
+ *     dbeta, db3 [128] may each be NULL (not wanted).  gamma may be NULL (1).  n == 1 is refused (EG_ERR_ARG) with torch's message.
+ * eg_pyramid_conv_bwd_data: dx = chain + ds (ds may be NULL).  From side 17 on an implicit GEMM on the f32-input matrix instruction,
+ *     weights read transposed with the taps flipped; the chain is eg_conv3x3_bwd_data's (output channel o ascending, within o tap
+ *     k = 0 .. 8 reads dz at offset (k / 3 - 1, k % 3 - 1) against w3[o][c][8 - k], one fmaf chain from 0): the result equals
+ *     eg_conv3x3_bwd_data followed by eg_embed_res_bwd_input(w1 = NULL) bit for bit.  Up to side 16 it RUNS those two entry points
+ *     (their kernel there adds 16 partial chains; one matrix chain would give other bits).
+ * eg_pyramid_conv_bwd_weight: dw3[o][c][ky][kx] = sum_{b, y, x} dz[b, o, y, x] x[b, c, y + ky - 1, x + kx - 1] on the matrix
+ *     instruction at every side.  Its order of summation is its own, a function of (batch, side) alone (csrc/pyramid_train.hip):
+ *     one chain per 32 x 8 pixel tile, tile sums in chains of 256, at most 64 slices added by the front-end's slice sum -- the
+ *     workspace does not grow with the pixel count.
+ * eg_pyramid_train_workspace_bytes: one workspace for a block's calls on one stream (eg_bn2d_train_fwd at 128 channels included):
+ *     chunk sums + at most 64 x 589,824 B of slices; 0 where the shapes are out of range.
+ * All: the caller's stream, no allocation, no synchronisation, no atomics; every sum has a fixed order in chains of at most 256
+ * terms (bit-identical from run to run), capturable.  EG_ERR_ARG, nothing launched: a NULL required pointer, batch or a side < 1,
+ * side_out > side, p outside [0, 1), an output aliasing an input or another output, n == 1 (eg_pyramid_act_bwd).
+ * EG_ERR_UNSUPPORTED, nothing launched: a side above 512, batch above 65535 or batch side^2 >= 2^31. */
+size_t eg_pyramid_train_workspace_bytes(int batch, int side, int side_out);
+int eg_pyramid_conv_fwd(const float* x, int batch, int side, const float* w3, const float* b3, float* z, eg_stream_t stream);
+int eg_pyramid_act_fwd(const float* y, const float* x, int batch, int side, int side_out, float p, uint64_t seed, float* keep, int* idx,
+                       float* out, eg_stream_t stream);
+int eg_pyramid_act_bwd(const float* dout, const float* out, const float* keep, const int* idx, const float* z, const float* save_mean,
+                       const float* save_invstd, const float* gamma, int batch, int side, int side_out, void* workspace, float* ds,
+                       float* dz, float* dgamma, float* dbeta, float* db3, eg_stream_t stream);
+int eg_pyramid_conv_bwd_data(const float* dz, const float* w3, const float* ds, int batch, int side, float* dx, eg_stream_t stream);
+int eg_pyramid_conv_bwd_weight(const float* x, const float* dz, int batch, int side, void* workspace, float* dw3, eg_stream_t stream);
 
 /* ---- node-feature packing (the step right before the hot path) -------------------------------------------
  * Reference: the per-sample loops at the tail of create_node_pixels (src/core/models.py:498-537, :590-636,

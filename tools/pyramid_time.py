@@ -16,6 +16,14 @@ Legs:
              synchronise) and replayed from one captured graph, both routes.
     model    model(x=frames, edge_index=...) of nn.CNNHierarchicalPatchModel at 224 / 7 with enable_hip_graph(): the torch modules
              (MIOpen) against enable_hip_pyramid(), ms per frame.
+    train    (only with --train, and then alone)  the training route, per block input side 224, 128, 64, 32, 16, 8, 4: every new
+             entry point beside what it replaces -- eg_pyramid_conv_fwd against eg_embed_conv_fwd, eg_pyramid_conv_bwd_data against
+             eg_conv3x3_bwd_data + eg_embed_res_bwd_input, eg_pyramid_conv_bwd_weight against eg_conv3x3_bwd_weight (batch 1 only: the
+             old entry point's workspace is one slice of the whole gradient per 32 x 8 tile; the new one is also timed alone at batch
+             8) -- replayed from captured graphs as in `block`; then the whole block forward + backward and the whole pyramid at batch
+             1 and 8, ops.pyramid_block_train against CNNResBlock from torch modules (the route training took before), eager and
+             replayed.  The outputs of old and new entry points are compared before anything is timed (torch.equal for the forward and
+             the data gradient, 1e-4 of the largest entry for the weight gradient, whose order of summation is its own).
 Prints one line per figure and a JSON summary line; with a path, appends what it printed to that file.  No gate."""
 import json
 import os
@@ -28,19 +36,22 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from echoglad_amd import ops  # noqa: E402
-from echoglad_amd.nn import CNNHierarchicalPatchModel  # noqa: E402
+from echoglad_amd.nn import CNNHierarchicalPatchModel, CNNResBlock  # noqa: E402
+from echoglad_amd.ops import embedder as E  # noqa: E402
 from echoglad_amd.synthetic import fill_state_dict  # noqa: E402
 from echoglad_amd.topology import HierTopology, TopologySpec  # noqa: E402
 
 WARMUP, ITERS, PAIRS, CALLS = 3, 20, 3, 10
 ROOF_TF = 157.3
 DEV = "cuda:0"
-_lines = []
+_out = None             # the text file every printed line is appended to, as it is printed
 
 
 def say(text):
     print(text, flush=True)
-    _lines.append(text)
+    if _out:
+        with open(_out, "a") as f:
+            f.write(text + "\n")
 
 
 def block_params(seed):
@@ -180,17 +191,145 @@ def model_legs(result):
         result["model"][f"b{B}"] = out
 
 
+SIDES = ((224, 128), (128, 64), (64, 32), (32, 16), (16, 8), (8, 4), (4, 2))
+
+
+def _bytes(name, *args):
+    return max(int(E.raw(name, *args)), 256)
+
+
+def train_entry_legs(result):
+    """Every new entry point beside what it replaces, device time per call."""
+    w, b, _ = block_params(1)
+    C = 128
+    for B in (1, 8):
+        for side, nxt in SIDES:
+            g = torch.Generator().manual_seed(side)
+            x, dz, ds = (torch.randn(B, C, side, side, generator=g).to(DEV) for _ in range(3))
+            new = lambda: torch.empty(B, C, side, side, device=DEV)
+            calls = CALLS if B * side * side > 64 * 64 else 4 * CALLS
+            tag = f"side {side}, batch {B}"
+            legs = {}
+            # forward
+            z0, z1 = new(), new()
+            old_f = lambda: E.call("eg_embed_conv_fwd", x, B, C, side, w, b, C, z0)
+            new_f = lambda: E.call("eg_pyramid_conv_fwd", x, B, side, w, b, z1)
+            old_f(), new_f()
+            assert torch.equal(z0, z1), tag
+            legs["conv_fwd"] = windows(f"conv_fwd {tag}", {"mfma": graphed(new_f, calls), "vector": graphed(old_f, calls)})
+            # data gradient
+            d0, d1 = new(), new()
+
+            def old_d():
+                E.call("eg_conv3x3_bwd_data", dz, w, B, C, side, C, side, 0, d0, None, None)
+                E.call("eg_embed_res_bwd_input", ds, None, B, C, C, side, d0)
+            new_d = lambda: E.call("eg_pyramid_conv_bwd_data", dz, w, ds, B, side, d1)
+            old_d(), new_d()
+            assert torch.equal(d0, d1), tag
+            legs["conv_bwd_data"] = windows(f"conv_bwd_data {tag}", {"new": graphed(new_d, calls), "old": graphed(old_d, calls)})
+            # weight gradient
+            g1 = torch.empty(C, C, 3, 3, device=DEV)
+            ws1 = torch.empty(_bytes("eg_pyramid_train_workspace_bytes", B, side, side), dtype=torch.uint8, device=DEV)
+            new_w = lambda: E.call("eg_pyramid_conv_bwd_weight", x, dz, B, side, ws1, g1)
+            if B == 1:
+                g0 = torch.empty(C, C, 3, 3, device=DEV)
+                ws0 = torch.empty(_bytes("eg_frontend_train_workspace_bytes", B, C, C, side), dtype=torch.uint8, device=DEV)
+                old_w = lambda: E.call("eg_conv3x3_bwd_weight", x, C, side, None, 0, B, side, dz, C, ws0, g0)
+                old_w(), new_w()
+                err = float((g0 - g1).abs().max()) / float(g0.abs().max())
+                assert err < 1e-4, (tag, err)
+                legs["conv_bwd_weight"] = windows(f"conv_bwd_weight {tag} (workspace {ws1.numel() / 2 ** 20:.1f} MiB against "
+                                                  f"{ws0.numel() / 2 ** 20:.1f} MiB)", {"mfma": graphed(new_w, calls), "vector": graphed(old_w, calls)})
+            else:
+                legs["conv_bwd_weight"] = windows(f"conv_bwd_weight {tag} (workspace {ws1.numel() / 2 ** 20:.1f} MiB; the old entry "
+                                                  f"point would take {_bytes('eg_frontend_train_workspace_bytes', B, C, C, side) / 2 ** 20:.1f} MiB)",
+                                                  {"mfma": graphed(new_w, calls)})
+            flop = 2.0 * 9 * C * C * B * side * side
+            say("    " + ", ".join(f"{k} {flop / list(v.values())[0]['us'] / 1e6:.1f} TF/s" for k, v in legs.items()) + f" of {ROOF_TF} (new route)")
+            for k, v in legs.items():
+                keys = list(v)
+                if len(keys) == 2:
+                    a, p = v[keys[0]], v[keys[1]]
+                    v["new_not_slower_beyond_the_spreads"] = a["us"] - p["us"] <= a["spread"] * a["us"] + p["spread"] * p["us"]
+            result["train"][f"entries_{side}_b{B}"] = legs
+
+
+def _torch_block(width, seed):
+    torch.manual_seed(seed)
+    return CNNResBlock(in_channels=128, padding=1, out_channels=128, kernel_size=3, out_size=width, cnn_dropout_p=0.1).to(DEV).train()
+
+
+def _chain(blocks, hip):
+    """forward + backward of a chain of CNNResBlocks from `frames` (a leaf that asks for its gradient, as behind a trainable embedder)."""
+    def run(frames, dout):
+        x = frames
+        for i, blk in enumerate(blocks):
+            if hip:
+                x = ops.pyramid_block_train(x, blk.conv.weight, blk.conv.bias, blk.bn, blk.pool.output_size[0], blk.dropout.p, 1000 + i)
+            else:
+                x = blk(x)
+        x.backward(dout)
+    return run
+
+
+def _safely(make, what):
+    try:
+        return make()
+    except Exception as e:                                # a route that cannot be captured is a finding, not the end of the tool
+        say(f"    {what}: not measured ({type(e).__name__}: {str(e).splitlines()[0][:160]})")
+        torch.cuda.synchronize()
+        return None
+
+
+def train_block_legs(result):
+    """The whole block and the whole pyramid, forward + backward, HIP against the torch modules."""
+    cases = [(f"block {side} -> {nxt}", [nxt], side) for side, nxt in SIDES] + [("pyramid 224 / 7", [w for _, w in SIDES], 224)]
+    for B in (1, 8):
+        for name, widths, side in cases:
+            blocks = [_torch_block(w, 20 + i) for i, w in enumerate(widths)]
+            params = [q for blk in blocks for q in blk.parameters()]
+            frames = torch.randn(B, 128, side, side, generator=torch.Generator().manual_seed(side)).to(DEV).requires_grad_()
+            dout = torch.randn(B, 128, widths[-1], widths[-1], generator=torch.Generator().manual_seed(7)).to(DEV)
+
+            def step(hip):
+                run = _chain(blocks, hip)
+
+                def fn():
+                    for q in params + [frames]:
+                        q.grad = None
+                    run(frames, dout)
+                return fn
+            e = windows(f"train {name}, batch {B}, eager", {"hip": eager(step(True)), "torch": eager(step(False))})
+            runs = {}
+            for key, hip in (("hip", True), ("torch", False)):
+                side_stream = torch.cuda.Stream()             # (torch.cuda.graph wants its warm-up on a side stream for autograd)
+                side_stream.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side_stream):
+                    r = _safely(lambda: graphed(step(hip), 1), f"{key} replayed")
+                torch.cuda.current_stream().wait_stream(side_stream)
+                if r is not None:
+                    runs[key] = r
+            g = windows(f"train {name}, batch {B}, replayed", runs) if runs else {}
+            result["train"][f"{name.replace(' ', '_')}_b{B}"] = {"eager": e, "replayed": g}
+            del blocks, params, frames
+            torch.cuda.empty_cache()
+
+
 def main():
+    global _out
     assert torch.cuda.is_available(), "pyramid_time.py measures on a GPU"
+    argv = [a for a in sys.argv[1:] if a != "--train"]
+    _out = argv[0] if argv else None
     result = {"tool": "pyramid_time", "device": torch.cuda.get_device_name(0), "iters": ITERS, "calls_per_graph": CALLS, "pairs": PAIRS,
-              "block": {}, "pyramid": {}, "model": {}}
-    block_legs(result)
-    pyramid_legs(result)
-    model_legs(result)
+              "block": {}, "pyramid": {}, "model": {}, "train": {}}
+    if "--train" in sys.argv[1:]:
+        train_entry_legs(result)
+        train_block_legs(result)
+    else:
+        block_legs(result)
+        pyramid_legs(result)
+        model_legs(result)
     say(json.dumps(result))
-    if len(sys.argv) > 1:
-        with open(sys.argv[1], "a") as f:
-            f.write("\n".join(_lines) + "\n")
     return 0
 
 
