@@ -164,6 +164,9 @@ __global__ __launch_bounds__(PK_THREADS) void k_conv1x1_relu_pack(const ConvPack
     }
 }
 
+// the kernels move 16 bytes per lane on the node rows, on a bias, and on a level map whose plane size is a multiple of 4 floats
+static inline bool misaligned16(const void* p) { return ((uintptr_t)p & 15) != 0; }
+
 static int fill_pack(const void* const* maps, const int* side, int n_levels, int batch, int64_t n_rows, int64_t row_offset,
                      bool reverse, PackArgs& a) {
     if (!maps || !side || n_levels < 1 || n_levels > PK_MAX_LEVELS || batch < 1 || n_rows < 1 || row_offset < 0)
@@ -175,6 +178,7 @@ static int fill_pack(const void* const* maps, const int* side, int n_levels, int
     for (int l = 0; l < n_levels; ++l) {
         if (!maps[l] || side[l] < 1) return set_error(EG_ERR_ARG, "NULL level map or bad side");
         const int64_t P = (int64_t)side[l] * side[l];
+        if ((P & 3) == 0 && misaligned16(maps[l])) return set_error(EG_ERR_ARG, "a level map with side * side % 4 == 0 must be 16-byte aligned");
         if (reverse) a.gmap[l] = (float*)maps[l]; else a.map[l] = (const float*)maps[l];
         a.side[l] = side[l]; a.row0[l] = (int)row; a.tile0[l] = tiles;
         row += P;
@@ -193,7 +197,7 @@ extern "C" {
 
 int eg_pack_levels(const float* const* level_maps, const int* level_side, int n_levels, int batch, int64_t n_rows,
                    int64_t row_offset, float* nodes, eg_stream_t stream) {
-    if (!nodes) return set_error(EG_ERR_ARG, "nodes is NULL");
+    if (!nodes || misaligned16(nodes)) return set_error(EG_ERR_ARG, "nodes is NULL or not 16-byte aligned");
     PackArgs a{};
     int rc = fill_pack((const void* const*)level_maps, level_side, n_levels, batch, n_rows, row_offset, false, a);
     if (rc != EG_OK) return rc;
@@ -205,7 +209,7 @@ int eg_pack_levels(const float* const* level_maps, const int* level_side, int n_
 
 int eg_unpack_levels(const float* nodes, float* const* level_maps, const int* level_side, int n_levels, int batch,
                      int64_t n_rows, int64_t row_offset, eg_stream_t stream) {
-    if (!nodes) return set_error(EG_ERR_ARG, "nodes is NULL");
+    if (!nodes || misaligned16(nodes)) return set_error(EG_ERR_ARG, "nodes is NULL or not 16-byte aligned");
     PackArgs a{};
     int rc = fill_pack((const void* const*)level_maps, level_side, n_levels, batch, n_rows, row_offset, true, a);
     if (rc != EG_OK) return rc;
@@ -219,6 +223,7 @@ int eg_conv1x1_relu_pack_levels(const float* const* level_feats, const float* co
                                 const int* level_channels, const int* level_side, int n_levels, int batch, int64_t n_rows,
                                 int64_t row_offset, float* nodes, eg_stream_t stream) {
     if (!nodes || !level_feats || !level_weights || !level_channels || !level_side) return set_error(EG_ERR_ARG, "NULL argument");
+    if (misaligned16(nodes)) return set_error(EG_ERR_ARG, "nodes must be 16-byte aligned");
     if (n_levels < 1 || n_levels > PK_MAX_LEVELS || batch < 1 || n_rows < 1 || row_offset < 0) return set_error(EG_ERR_ARG, "bad argument");
     if (n_rows * (int64_t)batch >= (1ll << 31)) return set_error(EG_ERR_ARG, "batch * rows exceeds int32");
     ConvPackArgs a{};
@@ -229,6 +234,8 @@ int eg_conv1x1_relu_pack_levels(const float* const* level_feats, const float* co
         if (!level_feats[l] || !level_weights[l] || level_side[l] < 1 || level_channels[l] < 1)
             return set_error(EG_ERR_ARG, "NULL level map / weight or bad side / channel count");
         const int64_t P = (int64_t)level_side[l] * level_side[l];
+        if (((P & 3) == 0 && misaligned16(level_feats[l])) || (level_biases && level_biases[l] && misaligned16(level_biases[l])))
+            return set_error(EG_ERR_ARG, "level features with side * side % 4 == 0 and every bias must be 16-byte aligned");
         a.feat[l] = level_feats[l]; a.w[l] = level_weights[l]; a.bias[l] = level_biases ? level_biases[l] : nullptr;
         a.cin[l] = level_channels[l]; a.side[l] = level_side[l]; a.row0[l] = (int)row; a.tile0[l] = tiles;
         row += P;

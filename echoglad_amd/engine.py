@@ -152,7 +152,11 @@ class GraphedTrainStep:
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         optimizer.zero_grad(set_to_none=True)
-        with torch.cuda.graph(self.graph, stream=stream):
+        # with a reducer the process group's watchdog thread may still poll the event of the last warm-up all-reduce: under the
+        # default "global" mode an event query from ANY thread during the capture is an error that terminates the process
+        # (hipErrorStreamCaptureUnsupported raised inside the watchdog), so only this thread's calls are policed then
+        mode = "global" if reducer is None else "thread_local"
+        with torch.cuda.graph(self.graph, stream=stream, capture_error_mode=mode):
             self.outputs = self._forward_backward(ops, bump=True)
             if reducer is None:
                 self.optimizer.step()

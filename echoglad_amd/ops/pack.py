@@ -125,12 +125,28 @@ def _square_sides(tensors, name: str, channels: Optional[int], batch: int):
     return [int(t.shape[2]) for t in tensors]
 
 
+def _off16(t: Optional[torch.Tensor], side: Optional[int] = None) -> bool:
+    """`t` would reach a 16-byte access of pack.hip at an address that is no multiple of 16: the node rows and a bias always move 16
+    bytes per lane, a level map / feature does where side * side % 4 == 0 (a contiguous view at an odd element offset of a packed
+    buffer; the entry points refuse such a pointer, so it is copied here, as ops.criteria does for eg_bce_*)."""
+    return t is not None and t.data_ptr() % 16 != 0 and (side is None or (side * side) % 4 == 0)
+
+
 def _pack_call(fn_name, maps, nodes, batch, n_rows, row_offset):
-    side = _ints(_square_sides(maps, "level map", C, batch))
+    sides = _square_sides(maps, "level map", C, batch)
+    side = _ints(sides)
+    at = nodes.clone() if _off16(nodes) else nodes
     if fn_name == "eg_pack_levels":
-        call(fn_name, _addresses(maps), side, len(maps), batch, n_rows, row_offset, nodes)
+        maps = [m.clone() if _off16(m, p) else m for m, p in zip(maps, sides)]
+        call(fn_name, _addresses(maps), side, len(maps), batch, n_rows, row_offset, at)
+        if at is not nodes:
+            nodes.copy_(at)
     else:
-        call(fn_name, nodes, _addresses(maps), side, len(maps), batch, n_rows, row_offset)
+        dst = [torch.empty_like(m) if _off16(m, p) else m for m, p in zip(maps, sides)]
+        call(fn_name, at, _addresses(dst), side, len(maps), batch, n_rows, row_offset)
+        for m, d in zip(maps, dst):
+            if d is not m:
+                m.copy_(d)
 
 
 class _PackLevelsFn(torch.autograd.Function):
@@ -187,8 +203,13 @@ def _conv_pack_call(feats, weights, biases, nodes, batch, n_rows, row_offset):
         if w.shape[0] != C:
             raise RuntimeError(f"level weight must be [{C}, {cin}(, 1, 1)], got {tuple(w.shape)}")
         _check_vec(b, "level bias", C)
+    feats = [f.clone() if _off16(f, p) else f for f, p in zip(feats, sides)]
+    biases = [b.clone() if _off16(b) else b for b in biases]
+    at = nodes.clone() if _off16(nodes) else nodes
     call("eg_conv1x1_relu_pack_levels", _addresses(feats), _addresses(weights), _addresses(biases), _ints(chans), _ints(sides), n, batch,
-         n_rows, row_offset, nodes)
+         n_rows, row_offset, at)
+    if at is not nodes:
+        nodes.copy_(at)
 
 
 class _ConvReluPackFn(torch.autograd.Function):

@@ -899,7 +899,9 @@ int eg_pyramid_conv_bwd_weight(const float* x, const float* dz, int batch, int s
  * level_maps: HOST array of n_levels (<= 16) DEVICE pointers to NCHW maps [batch, 128, side_l, side_l];
  * nodes: [batch * n_rows, 128]; level l lands at rows row_offset + sum_{k<l} side_k^2 of every frame, row-major
  * (h, w).  Rows outside the levels (connection / coordinate rows) are not touched.
- * eg_unpack_levels is the reverse copy (the gradient of the packing w.r.t. the maps). */
+ * eg_unpack_levels is the reverse copy (the gradient of the packing w.r.t. the maps).
+ * 16 bytes per lane: nodes, every bias, and a level map / feature with side_l^2 % 4 == 0 must be 16-byte aligned
+ * (EG_ERR_ARG otherwise, before any launch); other levels go element by element and need 4 bytes. */
 int eg_pack_levels(const float* const* level_maps, const int* level_side, int n_levels, int batch, int64_t n_rows,
                    int64_t row_offset, float* nodes, eg_stream_t stream);
 int eg_unpack_levels(const float* nodes, float* const* level_maps, const int* level_side, int n_levels, int batch,

@@ -3,20 +3,14 @@ import numpy as np
 import pytest
 import torch
 
+import pool_reference as R
+from coord_reference import FACTOR, ULP, Report
 from gpu_util import DEV, model_pair
 from fixtures_util import initial_coords, synthetic_frames
+from pool_reference import pack_rows as _reference_pack
 from echoglad_amd import ops
 
 pytestmark = pytest.mark.gpu
-
-
-def _reference_pack(maps, batch, n_rows, row_offset):
-    """models.py:511-537 / :726-756: per frame, map[i].permute(1, 2, 0).reshape(-1, 128) of every level, concatenated."""
-    out = torch.zeros(batch, n_rows, 128, dtype=maps[0].dtype, device=maps[0].device)
-    for i in range(batch):
-        x = torch.cat([m[i].permute(1, 2, 0).reshape(-1, 128) for m in maps], dim=0)
-        out[i, row_offset:row_offset + x.shape[0]] = x
-    return out.reshape(batch * n_rows, 128)
 
 
 @pytest.mark.parametrize("sides,batch,extra_front,extra_back", [
@@ -58,35 +52,92 @@ def test_create_node_pixels_matches_oracle(frame, naux, coord, main_only):
     assert float((got - want).abs().max()) <= 2e-6 * max(1.0, float(want.abs().max()))
 
 
+# the small cases whose seed meets the ReLU condition of test_gpu_pool_pack_fp64.py (float32 mask == float64 mask on the references,
+# min|s64| >= 64 max|s32 - s64|): their gradients fall under the float64 rule too.  With 10^5 .. 10^7 pre-activations no seed does
+# (none of 400 tried on the CPU for the other two): some |s| is always within rounding of the kink, so there the gradients keep the
+# bound they had against torch's float32, next to the rule on the values.
+CONV_RULE_SEED = {((17,), (1,), 2, 0, 0): 2}
+
+
+def _decoder_shape_on_the_device(sides, chans, batch, n_rows, front, capsys):
+    """The UNet variant's decoder (17 M node features): the float64 rule evaluated with torch float64 on the device."""
+    gen = torch.Generator(device=DEV).manual_seed(sum(sides) + sum(chans))
+    mk = lambda *shape, s=1.0: (torch.randn(*shape, device=DEV, generator=gen) * s).requires_grad_(True)
+    feats = [mk(batch, c, sd, sd) for sd, c in zip(sides, chans)]
+    ws = [mk(128, c, s=c ** -0.5) for c in chans]
+    bs = [mk(128, s=0.5) for _ in chans]
+    got = ops.conv1x1_relu_pack_levels(feats, ws, bs, batch, n_rows, front)
+    conv = lambda f, w, b, dt: torch.einsum("oc,bcij->boij", w.detach().to(dt), f.detach().to(dt)) + b.detach().to(dt).view(1, 128, 1, 1)
+    with torch.no_grad():
+        ref64 = _reference_pack([torch.relu(conv(f, w, b, torch.float64)) for f, w, b in zip(feats, ws, bs)], batch, n_rows, front)
+        scale = _reference_pack([conv(f.abs(), w.abs(), b.abs(), torch.float64) for f, w, b in zip(feats, ws, bs)], batch, n_rows, front)
+    maps = [torch.relu(torch.nn.functional.conv2d(f, w.view(128, -1, 1, 1), b)) for f, w, b in zip(feats, ws, bs)]
+    want = _reference_pack(maps, batch, n_rows, front)
+    ref_err = float((want.detach().double() - ref64).abs().max())
+    err = (got.detach().double() - ref64).abs()
+    tol = FACTOR * ref_err + 8 * ULP * scale
+    old = 1e-5 * max(1.0, float(want.detach().abs().max()))
+    with capsys.disabled():
+        print(f"\n  conv-pack decoder shape: max|kernel - fp64| {float(err.max()):.3e}, max|torch32 - fp64| {ref_err:.3e}, worst err / tol "
+              f"{float((err / tol).max()):.3f}; largest tolerance of the rule {float(tol.max()):.3e}, the bound it replaces {old:.3e}")
+    assert bool((err <= tol).all())
+    return feats, ws, bs, got, maps, want
+
+
 @pytest.mark.parametrize("sides,chans,batch,extra_front,extra_back", [
     ([2, 4, 8, 16, 32, 64, 128, 224], [512, 256, 128, 64, 32, 16, 8, 4], 2, 0, 0),      # the UNet variant's decoder (models.py:678-683)
     ([2, 4, 30], [40, 7, 3], 2, 4, 4), ([17], [1], 2, 0, 0), ([1, 3, 65], [33, 64, 5], 1, 2, 0)])
-def test_conv1x1_relu_fused_into_the_packing(sides, chans, batch, extra_front, extra_back):
+def test_conv1x1_relu_fused_into_the_packing(sides, chans, batch, extra_front, extra_back, capsys):
     """eg_conv1x1_relu_pack_levels == F.relu(Conv2d(C_l, 128, 1)(features[l])) + the reference's permute / cat
-    (models.py:707-710, :726-756), values and gradients (features, weights, biases)."""
-    rs = np.random.RandomState(sum(sides) + sum(chans))
-    mk = lambda *shape, s=1.0: torch.from_numpy((rs.standard_normal(shape) * s).astype(np.float32)).to(DEV).requires_grad_(True)
-    feats = [mk(batch, c, sd, sd) for sd, c in zip(sides, chans)]
-    convs = [torch.nn.Conv2d(c, 128, kernel_size=1).to(DEV) for c in chans]
+    (models.py:707-710, :726-756).  Values: every element against float64 under the rule of coord_reference.Report.check with
+    scale = |W||x| + |b| (ReLU is 1-Lipschitz: no margin, no element left out, a differing zero pattern is an error like any other).
+    Gradients (features, weights, biases): under the same rule where the case's seed keeps every pre-activation away from the
+    kink (CONV_RULE_SEED), and within 2e-4 of torch's float32 everywhere."""
     n_rows = extra_front + sum(s * s for s in sides) + extra_back
-    got = ops.conv1x1_relu_pack_levels(feats, [m.weight for m in convs], [m.bias for m in convs], batch, n_rows, extra_front)
-    maps = [torch.relu(m(f)) for m, f in zip(convs, feats)]
-    want = _reference_pack(maps, batch, n_rows, extra_front)
-    assert float((got - want).abs().max()) <= 1e-5 * max(1.0, float(want.abs().max()))
-    assert torch.equal((got == 0), (want == 0)) or float(((got == 0) != (want == 0)).float().mean()) < 1e-5      # same ReLU pattern
-    g = torch.from_numpy(rs.standard_normal(tuple(got.shape)).astype(np.float32)).to(DEV)
-    params = feats + [m.weight for m in convs] + [m.bias for m in convs]
-    got_g = torch.autograd.grad(got, params, g)
-    want_g = torch.autograd.grad(want, params, g)
-    for a, b in zip(got_g, want_g):
-        assert float((a - b).abs().max()) <= 2e-4 * max(1.0, float(b.abs().max()))
-    # the model-level tail: the same through HierarchicalPatchModel.pack_node_features_linear on the default shape
+    case = (tuple(sides), tuple(chans), batch, extra_front, extra_back)
     if sides[-1] == 224:
+        feats, ws, bs, got, maps, want = _decoder_shape_on_the_device(sides, chans, batch, n_rows, extra_front, capsys)
+        g = torch.randn(tuple(got.shape), device=DEV, generator=torch.Generator(device=DEV).manual_seed(1))
+        params = feats + ws + bs
+        for a, b in zip(torch.autograd.grad(got, params, g), torch.autograd.grad(want, params, g)):
+            assert float((a - b).abs().max()) <= 2e-4 * max(1.0, float(b.abs().max()))
+        # the model-level tail: the same through HierarchicalPatchModel.pack_node_features_linear on the default shape
+        convs = [torch.nn.Conv2d(c, 128, kernel_size=1).to(DEV) for c in chans]
+        with torch.no_grad():
+            for m, w, b in zip(convs, ws, bs):
+                m.weight.copy_(w.view_as(m.weight))
+                m.bias.copy_(b)
         hip, _ = model_pair(224, 7, 1)
         with torch.no_grad():
             a = hip.pack_node_features_linear([f.detach() for f in feats], convs, batch)
             b = hip.pack_node_features([m.detach() for m in maps], batch)
         assert float((a - b).abs().max()) <= 1e-5 * max(1.0, float(b.abs().max()))
+        return
+    fx = R.conv_fixture(*case, "all", CONV_RULE_SEED.get(case, sum(sides) + sum(chans)))
+    r64 = R.conv_pack64(fx["feats"], fx["weights"], fx["biases"], batch, n_rows, extra_front, dnodes=fx["dnodes"])
+    r32 = R.conv_torch32(fx)
+    same, ratio = R.relu_margin(r64["s"], r32["s"])
+    if case in CONV_RULE_SEED:
+        assert same and ratio >= R.MARGIN, (same, ratio)              # on the references alone, before the kernel runs
+    dev = lambda t: t.to(DEV).requires_grad_(True)
+    feats, ws, bs = [dev(t) for t in fx["feats"]], [dev(t) for t in fx["weights"]], [dev(t) for t in fx["biases"]]
+    got = ops.conv1x1_relu_pack_levels(feats, ws, bs, batch, n_rows, extra_front)
+    got_g = torch.autograd.grad(got, feats + ws + bs, fx["dnodes"].to(DEV))
+    rep = Report()
+    rep.check("node rows", got, r64["out"], r32["out"], r64["scale"])
+    n = len(sides)
+    want_g = r32["dfeat"] + r32["dw"] + r32["db"]
+    for a, b in zip(got_g, want_g):
+        assert float((a.cpu() - b).abs().max()) <= 2e-4 * max(1.0, float(b.abs().max()))
+    if case in CONV_RULE_SEED:
+        for key, lo in (("dfeat", 0), ("dw", n), ("db", 2 * n)):
+            for l in range(n):
+                rep.check(key, got_g[lo + l], r64[key][l], r32[key][l], r64[key + "_scale"][l])
+    tol = FACTOR * rep.rows["node rows"][2] + 8 * ULP * float(r64["scale"].max())
+    with capsys.disabled():
+        print(rep.table(f"conv-pack {case} (min|s64| / max|s32 - s64| = {ratio:.1f}, masks equal: {same})"))
+        print(f"    largest tolerance of the rule on the values {tol:.3e}, the bound it replaces {1e-5 * max(1.0, float(r32['out'].abs().max())):.3e}")
+    assert not rep.failed(), rep.failed()
 
 
 def test_conv_pack_rejects_bad_arguments():
@@ -144,7 +195,7 @@ def test_unet_variant_example_end_to_end(frame, naux, coord):
 @pytest.mark.parametrize("frame,sides,batch,chans", [(224, [2, 4, 8, 16, 32, 64, 128], 2, 128), (64, [2, 4, 8, 16, 32, 64], 2, 128),
                                                       (30, [2, 4, 8], 3, 128), (31, [2, 4, 8, 16], 2, 8), (448, [2, 4, 8, 16, 32, 64, 128, 256], 1, 4),
                                                       (16, [3, 5, 16], 2, 16), (256, [2, 4, 8, 16, 32, 64, 128], 1, 16), (8, [2], 1, 128)])
-def test_avg_pool_pyramid_is_adaptive_avg_pool2d_for_every_level(frame, sides, batch, chans):
+def test_avg_pool_pyramid_is_adaptive_avg_pool2d_for_every_level(frame, sides, batch, chans, capsys):
     """models.py:511-521: F.adaptive_avg_pool2d(frame, (2^g, 2^g)) for every aux level -- all levels in one launch
     (eg_avg_pool_pyramid_fwd: exact block means of a coarser level taken as the mean of 2 x 2 finer ones, everything else summed
     window by window) against torch's own op on the CPU in float64, and the gradient (a gather, no atomics) against torch's
@@ -154,13 +205,27 @@ def test_avg_pool_pyramid_is_adaptive_avg_pool2d_for_every_level(frame, sides, b
     want = [torch.nn.functional.adaptive_avg_pool2d(x_cpu, (p, p)) for p in sides]
     x = x_cpu.detach().float().to(DEV).requires_grad_(True)
     got = ops.avg_pool_pyramid(x, sides)
-    for g, w, p in zip(got, want, sides):
+    # ... and under the float64 rule of coord_reference.Report.check (yardstick: torch's op on the CPU in float32, scale: the sum of
+    # the summands' magnitudes); the absolute thresholds stay next to it where the rule is not the tighter bound
+    x32 = x_cpu.detach().float().requires_grad_(True)
+    want32 = [torch.nn.functional.adaptive_avg_pool2d(x32, (p, p)) for p in sides]
+    rep, tols = Report(), []
+    for g, w, w32, sc, p in zip(got, want, want32, R.pool_fwd_scale(x_cpu, sides), sides):
         assert g.shape == w.shape
         assert float((g.detach().cpu().double() - w.detach()).abs().max()) < 2e-6, p
+        assert rep.check("pool forward", g, w, w32, sc), p
+        tols.append(FACTOR * float((w32.detach().double() - w.detach()).abs().max()) + 8 * ULP * float(sc.max()))
     ws = [torch.from_numpy(rs.standard_normal(tuple(w.shape))) for w in want]
     sum((w * k).sum() for w, k in zip(want, ws)).backward()
     sum((g * k.float().to(DEV)).sum() for g, k in zip(got, ws)).backward()
     assert float((x.grad.cpu().double() - x_cpu.grad).abs().max()) < 1e-5
+    sum((w * k.float()).sum() for w, k in zip(want32, ws)).backward()
+    dscale = R.pool_bwd_scale(ws, None, sides, x_cpu.shape)
+    assert rep.check("pool x.grad", x.grad, x_cpu.grad, x32.grad, dscale)
+    with capsys.disabled():
+        print(rep.table(f"avg_pool_pyramid F {frame}, sides {sides}"))
+        print(f"    largest tolerance of the rule: forward {max(tols):.3e} (threshold 2e-6), x.grad "
+              f"{FACTOR * rep.rows['pool x.grad'][2] + 8 * ULP * float(dscale.max()):.3e} (threshold 1e-5)")
     # bit-reproducible (torch's CUDA backward adds with float atomics)
     x2 = x.detach().clone().requires_grad_(True)
     sum((g * k.float().to(DEV)).sum() for g, k in zip(ops.avg_pool_pyramid(x2, sides), ws)).backward()
