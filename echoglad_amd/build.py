@@ -16,16 +16,19 @@ PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIBDIR = PKG / "lib"
 LIBNAME = "libechoglad_hip.so"
-SOURCES = ["graph.hip", "topo_tables.hip", "gcn_layer.hip", "gcn_layer_ps.hip", "gcn_layer_ps_split.hip", "conn.hip", "classifier.hip", "train.hip", "bn_act_tiles.hip", "cls_train.hip", "coord.hip", "coord_mlp.hip", "heatmap.hip", "pack.hip", "pool.hip", "adam.hip", "metrics.hip", "labels.hip", "frame_prep.hip", "frontend.hip", "frontend_train.hip", "embedder.hip", "pyramid_conv.hip", "pyramid_train.hip"]
+SOURCES = ["graph.hip", "topo_tables.hip", "gcn_layer.hip", "gcn_layer_ps.hip", "gcn_layer_ps_split.hip", "gcn_layer_ps_fold_split.hip", "conn.hip", "classifier.hip", "train.hip", "bn_act_tiles.hip", "cls_train.hip", "coord.hip", "coord_mlp.hip", "heatmap.hip", "pack.hip", "pool.hip", "adam.hip", "metrics.hip", "labels.hip", "frame_prep.hip", "frontend.hip", "frontend_train.hip", "embedder.hip", "pyramid_conv.hip", "pyramid_train.hip"]
 ARCH = "gfx950"
 # per-file flags and extra dependencies, and objects whose device code must hold no packed fp32 vector instruction.
 # gcn_layer_ps_split.hip (the bf16-path instantiations of the layer kernel, gcn_layer_ps.hip included) is compiled without them:
 # beside bf16 MFMAs they return wrong results now and then (see there).  The feature goes through -Xclang, which the driver cannot
 # scope to the device side (-Xarch_device refuses it, and there is no -m option for it); the host compilation ignores it.  A flag
 # that stopped taking effect must not go unnoticed: the object is disassembled and checked below.
-FILE_FLAGS = {"gcn_layer_ps_split.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
-FILE_DEPS = {"gcn_layer_ps_split.hip": ["gcn_layer_ps.hip"]}
+# gcn_layer_ps_fold_split.hip (the bf16 bodies of the folded last layer + heads, v_mfma_f32_16x16x32_bf16) likewise.
+_NO_PACKED = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+FILE_FLAGS = {"gcn_layer_ps_split.hip": _NO_PACKED, "gcn_layer_ps_fold_split.hip": _NO_PACKED}
+FILE_DEPS = {"gcn_layer_ps_split.hip": ["gcn_layer_ps.hip"], "gcn_layer_ps_fold_split.hip": ["gcn_layer_ps.hip"]}
 NO_PACKED_FP32 = ("gcn_layer_ps_split.hip",)
+NO_PACKED_FP32_16X16 = ("gcn_layer_ps_fold_split.hip",)
 LLVM_BIN = Path("/opt/rocm/lib/llvm/bin")
 
 
@@ -55,6 +58,14 @@ def packed_fp32_census(binary: Path):
     import re
     text = device_disassembly(binary)
     return len(re.findall(r"\bv_mfma_f32_32x32x16_bf16\b", text)), len(re.findall(r"\bv_pk_\w+_f32\b", text))
+
+
+def fold_split_census(binary: Path):
+    """(v_mfma_f32_16x16x32_bf16, packed fp32 vector instructions, kernels with scratch) in the device code of `binary`."""
+    import re
+    text = device_disassembly(binary)
+    return (len(re.findall(r"\bv_mfma_f32_16x16x32_bf16\b", text)), len(re.findall(r"\bv_pk_\w+_f32\b", text)),
+            len(re.findall(r"\bscratch_(?:load|store)\w*\b", text)))
 
 
 def hipcc() -> str:
@@ -114,6 +125,13 @@ def build(force: bool = False, verbose: bool = False, extra_flags=(), variant: s
             if n_mfma == 0 or n_packed != 0:
                 o.unlink()
                 raise RuntimeError(f"{src}: {n_mfma} bf16 MFMAs and {n_packed} packed fp32 instructions in the device code; "
+                                   "expected some and none (packed fp32 instructions beside bf16 MFMAs return wrong results)")
+        if src in NO_PACKED_FP32_16X16:
+            o = objdir / (Path(src).stem + ".o")
+            n_mfma, n_packed, _ = fold_split_census(o)
+            if n_mfma == 0 or n_packed != 0:
+                o.unlink()
+                raise RuntimeError(f"{src}: {n_mfma} 16x16x32 bf16 MFMAs and {n_packed} packed fp32 instructions in the device code; "
                                    "expected some and none (packed fp32 instructions beside bf16 MFMAs return wrong results)")
     target = lib_path() if not variant else LIBDIR / f"libechoglad_hip.{variant}.so"
     if force or _stale(target, objs):

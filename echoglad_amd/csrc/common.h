@@ -336,6 +336,7 @@ struct LayerCall {
     const float* kin = nullptr;         // child sums of x from the layer before / of out for the next one (producer/consumer kernel)
     float* kout = nullptr;
     const ClsArgs* cls = nullptr;       // fused heads (producer/consumer kernel)
+    const void* fold_lo = nullptr;      // ... folded, on the bf16 path: the pre-split lo planes of M and W1s (eg_gcn_layer_cls_fold_split_fwd)
     const float* jk_in = nullptr;       // running JumpingKnowledge maximum (producer/consumer kernel)
     float* jk_out = nullptr;
     float* agg_out = nullptr;           // train forward: receives the aggregated rows A_hat x ...

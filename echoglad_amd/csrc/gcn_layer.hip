@@ -709,6 +709,23 @@ int eg_gcn_layer_cls_fold_fwd(const eg_graph* g, int batch, const float* x, int 
     return public_rc(rc);
 }
 
+int eg_gcn_layer_cls_fold_split_fwd(const eg_graph* g, int batch, const float* x, int residual, const float* kidsum_in, const float* m1,
+                                    const float* w1s, const float* c1, const void* lo_planes, const float* w2, const float* s2,
+                                    const float* t2, const float* w3, const float* b3, int sigmoid, float* logits, eg_stream_t stream) {
+    if (!x || !logits || !m1 || !w1s || !c1 || !lo_planes || !w2 || !s2 || !t2 || !w3 || !b3) return set_error(EG_ERR_ARG, "NULL argument");
+    if (((uintptr_t)m1 | (uintptr_t)w1s | (uintptr_t)lo_planes) & 15) return set_error(EG_ERR_ARG, "m1, w1s and lo_planes must be 16-byte aligned");
+    if (!g || batch <= 0) return set_error(EG_ERR_ARG, "bad graph handle or batch");
+    if (g->kind != GRAPH_TOPO || g->topo.coord_base < g->n_nodes)
+        return set_error(EG_ERR_UNSUPPORTED, "the fused classifier needs a topology handle without coordinate nodes");
+    const eg::ClsArgs heads{w1s, nullptr, c1, w2, s2, t2, w3, b3, logits, sigmoid, g->topo.n_conn, (int)g->n_nodes - g->topo.n_conn, 1};
+    LayerCall c;
+    c.x = x; c.W = m1; c.residual = residual ? x : nullptr; c.kin = kidsum_in; c.cls = &heads; c.fold_lo = lo_planes;
+    const int rc = eg_launch_layer_ps(g, batch, c, (hipStream_t)stream);
+    if (rc == EG_ERR_UNSUPPORTED)
+        return set_error(EG_ERR_UNSUPPORTED, "the fused classifier needs eg_graph_fused_classifier_ok()");
+    return public_rc(rc);
+}
+
 unsigned eg_graph_ps_launches(const eg_graph* g) { return g ? g->ps_launches.load(std::memory_order_relaxed) : 0u; }
 unsigned eg_graph_layer_launches(const eg_graph* g) { return g ? g->layer_launches.load(std::memory_order_relaxed) : 0u; }
 

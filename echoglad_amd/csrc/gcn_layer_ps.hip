@@ -123,7 +123,11 @@ __device__ inline void ps_claim(int* __restrict__ counters, int group, int n_til
 // operands, six piece products per 16-k step (tile.h mfma_rowblock_bf16x6): fp32-accurate, 96 MFMAs of 32 cycles per tile instead
 // of 128 of 64, and beside them the vector datapath stays free for the SIMD's producer wave.  The W slice takes 96 VGPRs instead
 // of 64, so the residual rows are read one 32-row block at a time (RES_LATE, as with the fused heads).
-template <bool CLS, bool JK = false, int MODE = 0, bool DIAG = false, int FOLD = 0, bool SPLIT = false>
+// FSPLIT (FOLD only; gcn_layer_ps_fold_split.hip): the folded products on the bf16 matrix path as well, from the same exact 3-piece
+// splits, with v_mfma_f32_16x16x32_bf16 (tile.h fs_step).  The hi and mid planes of M and W1s stay in registers (128 VGPRs, what
+// wreg + wreg2 take); FOLD = 1 streams the two lo planes from a pre-split table (64 KB, L2-resident; it arrives in the `scale`
+// argument, which a folded launch does not use otherwise) through a ring of two 8-VGPR slots, FOLD = 2 keeps M's lo plane too.
+template <bool CLS, bool JK = false, int MODE = 0, bool DIAG = false, int FOLD = 0, bool SPLIT = false, bool FSPLIT = false>
 __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __restrict__ x, const float* __restrict__ W,
                                                                 const float* __restrict__ scale, const float* __restrict__ shift,
                                                                 float* __restrict__ out, const float* __restrict__ dis,
@@ -169,6 +173,7 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
     }
     static_assert(!FOLD || (CLS && !JK && MODE == 0), "FOLD is a form of the fused last layer without the running maximum");
     static_assert(!SPLIT || (!CLS && !JK && MODE == 0), "SPLIT is a form of the plain eval layer");
+    static_assert(!FSPLIT || FOLD != 0, "FSPLIT is a body of the folded forms");
     if (CLS) {
         if (FOLD) {
             if (tid < C) s_bn[tid] = ca.t1[tid];
@@ -188,7 +193,27 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
         // =========================== CONSUMER: channels 32*wave .. 32*wave+31 ===================================
         constexpr bool RES_LATE = CLS || SPLIT;        // (the fused-classifier and split variants have no registers for the residual prefetch)
         float wreg[64];
-        load_w_slice(W, wave, lane_k, a.transpose_w, wreg);
+        if constexpr (!FSPLIT) load_w_slice(W, wave, lane_k, a.transpose_w, wreg);
+        // FSPLIT: the pieces of M (and W1s), the resident lo plane of FOLD = 2, the ring of FOLD = 1: slot p & 1 holds the lo
+        // fragments of (matrix, step) p = 4 m + s; the table holds [p][wave][cb][lane] 16-byte entries
+        FsPlanes fw[2];
+        bf16x8 flo[4][2], ring[2][2];
+        // (a buffer load: one descriptor, one lane offset, the entry's place as the scalar offset -- eight 64-bit addresses
+        // kept across the tile loop were spilled)
+        const __amdgpu_buffer_rsrc_t lo_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(scale), 0, FSPLIT && FOLD == 1 ? 65536 : 0, 0x00020000);
+        const int lo_voff = (128 * wave + lane_k) * 16;
+        auto ring_load = [&](int p) {
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb)
+                ring[p & 1][cb] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(lo_rsrc, lo_voff, 8192 * p + 1024 * cb, 0));
+        };
+        if constexpr (FSPLIT) {
+            fs_load_w(W, wave, lane_k, fw[0], FOLD == 2 ? flo : nullptr);
+            if (FOLD == 1) {
+                fs_load_w(ca.w1, wave, lane_k, fw[1], nullptr);
+                ring_load(0); ring_load(1);
+            }
+        }
         // The per-channel scale of the epilogue (eval-mode BatchNorm folded by the caller) goes into the W slice -- lane
         // (i = l & 31) holds output channel 32 wave + i -- and the shift into the accumulators' initial value: the epilogue
         // is max + residual add, with no LDS or register operand of its own.
@@ -220,7 +245,7 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
         f32x4 t2v, w3v;
         float b3v = 0.f;
         if (CLS) {
-            load_w_slice(ca.w1, wave, lane_k, 0, wreg2);
+            if constexpr (!FSPLIT) load_w_slice(ca.w1, wave, lane_k, 0, wreg2);
             if (!FOLD) {
                 const float sv = ca.s1[32 * wave + (lane_k & 31)];      // the first head layer's BatchNorm scale, folded the same way
 #pragma unroll
@@ -581,7 +606,83 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
                     v.x = max_raw(v.x, 0.f); v.y = max_raw(v.y, 0.f); v.z = max_raw(v.z, 0.f); v.w = max_raw(v.w, 0.f);
                     *reinterpret_cast<f32x4*>(s_a + (32 * rb + j) * LDA + 32 * wave + 4 * h + 8 * g) = v;
                 };
-                if (!FOLD) {
+                if constexpr (FSPLIT) {
+                    // Step-major: for each (matrix, step) p all four row blocks, so that a lo fragment is fetched once per tile.
+                    // Unit u = 4 p + rb: 12 MFMAs on piece set u & 1; behind the first two, the guard of unit u - 1 frees the other
+                    // set (and, at rb = 0, the ring slot phase p - 1 read), the split of unit u + 1 is written into it beside the
+                    // other ten, the fragments of unit u + 2 are read.  The load for phase p + 1 goes out behind that guard of
+                    // (p, 0) -- a vector-memory write into an operand register obeys the rule of a VALU write --, the one for the
+                    // NEXT tile's phase 1 behind the chain's last guard: both in front of the tile's logit stores, so the wait at
+                    // the top of the next tile is for loads older than the stores (see s_cd above).  The accumulation order is
+                    // the unit order, the same for every tile.
+                    constexpr int NU = FOLD == 1 ? 32 : 16;
+                    const int j16f = lane & 15, kqf = lane >> 4;
+                    const float* pa = s_a + j16f * LDA + koff16(kqf);
+                    const float* px = s_x + j16f * LDA + koff16(kqf);
+                    auto frag = [&](int u, f32x4 (&r)[2]) {
+                        const f32x4* b = reinterpret_cast<const f32x4*>((u < 16 ? pa : px) + 16 * (u & 3) * LDA + 8 * ((u >> 2) & 3));
+                        r[0] = b[0]; r[1] = b[1];
+                    };
+                    f32x4v fa[4][2];
+#pragma unroll
+                    for (int cb = 0; cb < 2; ++cb) {
+                        const f32x4 q = *reinterpret_cast<const f32x4*>(s_bn + 32 * wave + 16 * cb + 4 * kqf);
+#pragma unroll
+                        for (int rb = 0; rb < 4; ++rb) fa[rb][cb] = f32x4v{q.x, q.y, q.z, q.w};
+                    }
+                    f32x4 raw[2][2];
+                    Pieces set[2];
+                    frag(0, raw[0]); frag(1, raw[1]);
+                    set[0] = fs_split3_x8(raw[0][0], raw[0][1]);
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int u = 0; u < NU; ++u) {
+                        const int p = u >> 2, rb = u & 3, m = p >> 2, s = p & 3;
+                        const Pieces& cur = set[u & 1];
+                        const bf16x8 (&wlo)[2] = FOLD == 1 ? ring[p & 1] : flo[s];
+                        keep_pieces(cur);
+                        fs_step<0>(fw[m].hi[s], fw[m].mid[s], wlo, cur, fa[rb]);
+                        if (u >= 1) {
+                            fs_operand_guard(fa[(u - 1) & 3][0], fa[(u - 1) & 3][1]);
+                            keep_pieces(set[(u + 1) & 1]);
+                            if (FOLD == 1 && rb == 0) {
+                                keep_lo(ring[(p + 1) & 1]);
+                                __builtin_amdgcn_sched_barrier(0);
+                                ring_load((p + 1) & 7);
+                            }
+                            if (u == 15) a_tile_done();         // (the last fragments of s_a went into set[1] a unit ago)
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (u + 1 < NU) set[(u + 1) & 1] = fs_split3_x8(raw[(u + 1) & 1][0], raw[(u + 1) & 1][1]);
+                        if (u + 2 < NU) frag(u + 2, raw[u & 1]);
+                        fs_step<1>(fw[m].hi[s], fw[m].mid[s], wlo, cur, fa[rb]);
+                        if (u + 1 < NU) {
+#pragma unroll
+                            for (int q = 0; q < 10; ++q) {          // one MFMA, then four of the split's vector instructions (groups of
+                                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // 2, 5 and 10 MFMAs measured 1 - 4 % slower per tile)
+                                __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+                            }
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    fs_operand_guard(fa[3][0], fa[3][1]);
+                    keep_pieces(set[0]);
+                    keep_pieces(set[1]);
+                    if (FOLD == 1) {
+                        keep_lo(ring[1]);
+                        __builtin_amdgcn_sched_barrier(0);
+                        ring_load(1);
+                    }
+                    a_tile_free();
+#pragma unroll
+                    for (int rb = 0; rb < 4; ++rb)
+#pragma unroll
+                        for (int cb = 0; cb < 2; ++cb) {
+                            const f32x4v z = fa[rb][cb];
+                            *reinterpret_cast<f32x4*>(s_a + (16 * rb + j16f) * LDA + 32 * wave + 16 * cb + 4 * kqf) =
+                                f32x4{max_raw(z.x, 0.f), max_raw(z.y, 0.f), max_raw(z.z, 0.f), max_raw(z.w, 0.f)};
+                        }
+                } else if (!FOLD) {
                     mfma_rowblock(s_x, 0, lane, wreg2, hc0);
                     mfma_rowblock_with(s_x, 32, lane, wreg2, hc1, [&](int c) { hidden_group(hc0, 0, c); });
                 } else {
@@ -641,8 +742,10 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
                     hb[b4][0] = hp[0]; hb[b4][1] = hp[1];
                 };
                 load_hidden(0); load_hidden(1);                       // rows 0..31 (ahead of the LDS writes below)
+                if constexpr (!FSPLIT) {                              // (FSPLIT: all 64 rows are written behind its chain)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) hidden_group(hc1, 1, g);
+                    for (int g = 0; g < 4; ++g) hidden_group(hc1, 1, g);
+                }
                 load_hidden(2); load_hidden(3);
                 // second / third layers per 16-row block: K = 32 on the MFMA (8 x 16x16x4), BN + ReLU + the 16-wide dot
                 // on the accumulator (4 outputs per lane, two cross-lane adds), as in classifier.hip
@@ -664,7 +767,8 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
 #pragma unroll
                 for (int b4 = 0; b4 < 4; ++b4) z[b4] = f32x4v{t2v.x, t2v.y, t2v.z, t2v.w};
                 // rows 0..31 first: their hidden values were written inside the chain above, so these MFMAs run while the
-                // writes of rows 32..63 and the reads behind them are in flight
+                // writes of rows 32..63 and the reads behind them are in flight (FSPLIT wrote all 64 rows behind its chain: there
+                // the order only lets the reads of rows 32..63 land behind the first MFMAs)
 #pragma unroll
                 for (int t = 0; t < 8; ++t)
 #pragma unroll
@@ -936,6 +1040,15 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
 // other instantiation keeps them (DESIGN_NOTES 9.8).
 using PsKernelFn = decltype(&k_gcn_layer_ps<false>);       // (every instantiation has the same signature; unevaluated: instantiates nothing)
 PsKernelFn ps_split_kernel(bool diag);
+// The bf16 bodies of the folded forms (FSPLIT) likewise: gcn_layer_ps_fold_split.hip, EG_PS_FOLD_SPLIT_TU, the same flags; a
+// consumer's partner on the SIMD is a producer wave of the same kernel.
+PsKernelFn ps_fold_split_kernel(bool diag, int fold);
+#ifdef EG_PS_FOLD_SPLIT_TU
+PsKernelFn ps_fold_split_kernel(bool diag, int fold) {
+    if (fold == 1) return diag ? k_gcn_layer_ps<true, false, 0, true, 1, false, true> : k_gcn_layer_ps<true, false, 0, false, 1, false, true>;
+    return diag ? k_gcn_layer_ps<true, false, 0, true, 2, false, true> : k_gcn_layer_ps<true, false, 0, false, 2, false, true>;
+}
+#endif
 #ifdef EG_PS_SPLIT_TU
 PsKernelFn ps_split_kernel(bool diag) {
     return diag ? k_gcn_layer_ps<false, false, 0, true, 0, true> : k_gcn_layer_ps<false, false, 0, false, 0, true>;
@@ -944,7 +1057,7 @@ PsKernelFn ps_split_kernel(bool diag) {
 
 }  // namespace eg
 
-#ifndef EG_PS_SPLIT_TU
+#if !defined(EG_PS_SPLIT_TU) && !defined(EG_PS_FOLD_SPLIT_TU)
 using namespace eg;
 
 int eg_launch_conn_prepass(const eg_graph* g, int batch, const float* x, int slot, hipStream_t stream, const float** base);
@@ -1010,11 +1123,16 @@ int eg_launch_layer_ps(const eg_graph* g, int batch, const LayerCall& c, hipStre
                 if (!fn) return set_error(EG_ERR_HIP, "a form of the layer kernel has no instantiation");
                 EG_HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             }
+            for (int i = 0; i < 4; ++i)
+                EG_HIP_TRY(hipFuncSetAttribute((const void*)ps_fold_split_kernel(i & 1, 1 + (i >> 1)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             if (dev >= 0 && dev < 64) attr_set[dev].store(true, std::memory_order_release);
         }
     }
     if (!ps_form_listed(form)) return set_error(EG_ERR_HIP, "the layer kernel has no such form");      // (only a listed form has its LDS)
-    const PsKernelFn kernel = ps_kernel(form);
+    // The folded forms have a second body, the bf16 one; the handle's layer_split knob picks it, as it picks the plain layer's
+    // split chain, when the caller brought the pre-split lo planes (eg_gcn_layer_cls_fold_split_fwd).
+    const bool fold_split = form.fold != 0 && g->knobs.layer_split != 0 && c.fold_lo != nullptr;
+    const PsKernelFn kernel = fold_split ? ps_fold_split_kernel(form.diag, form.fold) : ps_kernel(form);
     int* queue = nullptr;
     int slot = -1;
     {
@@ -1053,7 +1171,8 @@ int eg_launch_layer_ps(const eg_graph* g, int batch, const LayerCall& c, hipStre
     const ClsArgs none{};
     if (c.grid_out) *c.grid_out = (int)grid;
     eg::LaunchTimer timer(form.mode == 1 ? EG_LAUNCH_PS_TRAIN_FWD : form.mode >= 2 ? EG_LAUNCH_PS_DX : form.cls ? EG_LAUNCH_PS_CLS : EG_LAUNCH_PS_PLAIN, stream);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(PS_THREADS), lds, stream, c.x, c.W, c.scale, c.shift, c.out, g->dis, g->topo_dev,
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(PS_THREADS), lds, stream, c.x, c.W,
+                       fold_split ? static_cast<const float*>(c.fold_lo) : c.scale, c.shift, c.out, g->dis, g->topo_dev,
                        g->tiles_dev, g->segs_dev, g->pats_dev, g->patsq_dev, c.kin, c.kout, c.jk_in, c.jk_out, queue, a, c.cls ? *c.cls : none,
                        (const int*)g->rowptr, (const int*)g->colidx);
     g->commit_queue_slice(slot, stream);
@@ -1062,4 +1181,4 @@ int eg_launch_layer_ps(const eg_graph* g, int batch, const LayerCall& c, hipStre
     EG_HIP_TRY(hipGetLastError());
     return EG_OK;
 }
-#endif  // EG_PS_SPLIT_TU
+#endif  // neither split translation unit

@@ -19,7 +19,10 @@ inline bool operator==(const PsForm& a, const PsForm& b) {
     return a.cls == b.cls && a.jk == b.jk && a.mode == b.mode && a.diag == b.diag && a.fold == b.fold && a.split == b.split;
 }
 
-// Every instantiation that exists.  eg_launch_layer_ps grants each the large dynamic LDS block and launches nothing else.
+// The forms.  Each has one instantiation, except the four folded ones, which have a second body behind the same form (FSPLIT:
+// the products on the bf16 matrix path, gcn_layer_ps_fold_split.hip; eg_launch_layer_ps picks it from the handle's layer_split
+// knob when the call brings the pre-split lo planes).  eg_launch_layer_ps grants every body the large dynamic LDS block and
+// launches nothing else.
 constexpr PsForm PS_FORMS[] = {
     {false, false, 0, false, 0, false}, {false, false, 0, true, 0, false},     // plain eval layer, fp32 chain
     {false, false, 0, false, 0, true},  {false, false, 0, true, 0, true},      // ... split product (gcn_layer_ps_split.hip)

@@ -759,6 +759,87 @@ __device__ inline void mfma16_pair(const float* s_a, int row0, int lane, const f
     }
 }
 
+// ---- folded last layer + heads on the bf16 path: v_mfma_f32_16x16x32_bf16 ---------------------------------------------
+// A wave's 64 x 32 output is 4 row blocks x 2 column blocks of 16 x 16.  A operand = W pieces: lane (i = l & 15, kq = l >> 4)
+// holds W[32 w + 16 cb + i][koff16(kq) + 8 s + e], e = 0..7, for 32-k step s = 0..3 and column block cb; B operand = the LDS tile:
+// lane (j = l & 15, kq) reads a[row0 + j][koff16(kq) + 8 s + e] as two ds_read_b128.  In 16-byte units the address is
+// 33 (row0 + j) + koff16(kq) / 4 + 2 s (+ 1): modulo 16 slots that is j + const for kq and kq ^ 1 alike (they are 64 floats
+// apart), and a ds_read_b128 lane group holds j = 0..3, 12..15 of one kq and j = 4..11 of kq ^ 1 -- sixteen distinct slots, no
+// bank conflict at LDA = 132 (the argument of mfma16_pair).  D: lane (j, q = l >> 4), register r -> out[row0 + j][16 cb + 4 q + r].
+// fold_lo_table (ops/infer.py) lays the streamed lo plane out the same way: one 16-byte load per lane and (matrix, step, cb).
+// split3_x8 without the mask on the lo piece: pack_top16 takes the upper halves, so the bits are the same and a fragment costs 44
+// vector instructions instead of 52 (the folded chain is bound by its own vector issue: a 16x16x32 MFMA hides none of them).
+__device__ inline Pieces fs_split3_x8(const f32x4& q0, const f32x4& q1) {
+    u32x4 ph, pm, pl;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float hi[2], mid[2], lo[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const float a = 2 * e + i < 4 ? q0[2 * e + i] : q1[2 * e + i - 4];
+            hi[i] = split3_top16(a);
+            const float r = a - hi[i];
+            mid[i] = split3_top16(r);
+            lo[i] = r - mid[i];                      // (at most 8 significant bits, or a subnormal whose low half the pack drops)
+        }
+        ph[e] = pack_top16(hi[0], hi[1]); pm[e] = pack_top16(mid[0], mid[1]); pl[e] = pack_top16(lo[0], lo[1]);
+    }
+    return Pieces{__builtin_bit_cast(bf16x8, ph), __builtin_bit_cast(bf16x8, pm), __builtin_bit_cast(bf16x8, pl)};
+}
+
+struct FsPlanes { bf16x8 hi[4][2], mid[4][2]; };         // hi and mid plane of one matrix' slice: 2 x 32 VGPRs
+
+__device__ inline void fs_load_w(const float* __restrict__ W, int wave, int lane, FsPlanes& w, bf16x8 (*lo)[2]) {
+    const int i = lane & 15, k0 = koff16(lane >> 4);
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb) {
+        const f32x4* p = reinterpret_cast<const f32x4*>(W + (size_t)(32 * wave + 16 * cb + i) * C + k0);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const Pieces pc = split3_x8(p[2 * s], p[2 * s + 1]);
+            w.hi[s][cb] = pc.hi; w.mid[s][cb] = pc.mid;
+            if (lo) lo[s][cb] = pc.lo;
+        }
+    }
+}
+
+// The operand guard of mfma_operand_guard for two 16 x 16 accumulators (the last MFMAs issued wrote them; the matrix pipe runs in
+// issue order, so every earlier one has retired with them).
+__device__ inline void fs_operand_guard(const f32x4v& a, const f32x4v& b) {
+    __builtin_amdgcn_sched_barrier(0);
+    const int s0 = __builtin_amdgcn_readfirstlane(__float_as_int(a[0])), s1 = __builtin_amdgcn_readfirstlane(__float_as_int(b[0]));
+    asm volatile("" :: "s"(s0), "s"(s1));
+    asm volatile("s_nop 15" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+}
+__device__ inline void keep_lo(const bf16x8 (&lo)[2]) {
+    const u32x4 a = __builtin_bit_cast(u32x4, lo[0]), b = __builtin_bit_cast(u32x4, lo[1]);
+    asm volatile("" :: "v"(a.x), "v"(a.y), "v"(a.z), "v"(a.w), "v"(b.x), "v"(b.y), "v"(b.z), "v"(b.w));
+}
+
+// One 32-k step of one 16-row block: 2 column blocks x the six products of mfma_step_bf16x6, per accumulator in its order
+// (smallest terms first; lo.lo, lo.mid, mid.lo left out).  PART 0: the two lo.hi products; 1: the other ten.
+template <int PART>
+__device__ inline void fs_step(const bf16x8 (&whi)[2], const bf16x8 (&wmid)[2], const bf16x8 (&wlo)[2], const Pieces& ap, f32x4v (&acc)[2]) {
+#define FS_MFMA(w, a) for (int cb = 0; cb < 2; ++cb) acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[cb], a, acc[cb], 0, 0, 0)
+    if (PART == 0) {
+#pragma unroll
+        FS_MFMA(wlo, ap.hi);
+    } else {
+#pragma unroll
+        FS_MFMA(whi, ap.lo);
+#pragma unroll
+        FS_MFMA(wmid, ap.mid);
+#pragma unroll
+        FS_MFMA(wmid, ap.hi);
+#pragma unroll
+        FS_MFMA(whi, ap.mid);
+#pragma unroll
+        FS_MFMA(whi, ap.hi);
+    }
+#undef FS_MFMA
+}
+
 // ---- persistent tile walk ------------------------------------------------------------------
 // Tiles that are neighbours in the node order share halo rows (grid rows +-1, parents), so they
 // should be processed on the SAME XCD (same L2) at about the same time.  Three modes:

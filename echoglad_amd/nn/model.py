@@ -202,14 +202,17 @@ class HierarchicalPatchModel(nn.Module):
         return hit[1]
 
     def _folded_last(self):
-        """(m1, w1s, c1) of _heads.fold_last_into_heads: the last layer (it has no ReLU) inside the heads' first Linear, for
+        """(m1, w1s, c1, lo planes) -- _heads.fold_last_into_heads and ops.fold_lo_table: the last layer (it has no ReLU) inside the heads' first Linear, for
         eg_gcn_layer_cls_fold_fwd.  Cached on the versions the two tables above are cached on."""
         key = (tuple(_versions(l) for l in self.gnn_layers), tuple(_versions(c) for c in self.node_classifiers))
         hit = self._fold_cache.get("fold_last")
         if hit is None or hit[0] != key:
             w, scale, shift = self._folded_layers()[-1]
             packed = self._packed_classifier()
-            hit = (key, fold_last_into_heads(w, scale, shift, packed["w1"], packed["s1"], packed["t1"], bool(self.residual)))
+            folded = fold_last_into_heads(w, scale, shift, packed["w1"], packed["s1"], packed["t1"], bool(self.residual))
+            # ... and the lo planes of m1 and w1s the bf16 body streams (ops.fold_lo_table): held here, so that a captured graph
+            # sees stable addresses
+            hit = (key, folded + (ops.fold_lo_table(folded[0], folded[1]),))
             self._fold_cache["fold_last"] = hit
         return hit[1]
 

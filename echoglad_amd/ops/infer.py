@@ -74,20 +74,74 @@ def gcn_layer_cls_fwd(graph: Graph, batch: int, x: torch.Tensor, weight: torch.T
     return out
 
 
+def split3_planes(w: torch.Tensor):
+    """The exact 3-piece bf16 split of the kernels (csrc/tile.h split3), on the host side: float32 tensors hi, mid, lo whose low 16
+    bits are zero, hi + mid + lo == w bit for bit (|w| >= 2^-110; integer masks and two exact subtractions)."""
+    def top16(v):
+        return (v.contiguous().view(torch.int32) & -65536).view(torch.float32)
+    w = w.detach().to(torch.float32)
+    hi = top16(w)
+    r = w - hi
+    mid = top16(r)
+    return hi, mid, top16(r - mid)
+
+
+_KOFF = (0, 64, 32, 96)          # csrc/tile.h koff16: the k quarter a lane group kq reads
+
+
+def fold_lo_index(device=None):
+    """(channel, k) index tensors of the lo-plane table's layout [k-step 4][wave 4][column block 2][kq 4][i 16][e 8]: entry
+    = W[32 wave + 16 cb + i][koff(kq) + 8 step + e], the order in which the lanes of eg_gcn_layer_cls_fold_split_fwd fetch it."""
+    ar = lambda n: torch.arange(n, device=device)          # (made on `device`: no host-to-device copy, legal under stream capture)
+    s, wv, cb, kq, i, e = torch.meshgrid(ar(4), ar(4), ar(2), ar(4), ar(16), ar(8), indexing="ij")
+    ch = 32 * wv + 16 * cb + i
+    k = 64 * (kq & 1) + 32 * (kq >> 1) + 8 * s + e          # koff(kq) of _KOFF
+    return ch, k
+
+
+def fold_lo_table(m1: torch.Tensor, w1s: torch.Tensor) -> torch.Tensor:
+    """The lo planes of m1 and w1s as bf16 bit patterns (int16 [2, 4, 4, 2, 4, 16, 8], 64 KB) in the kernel's fetch order."""
+    ch, k = fold_lo_index(m1.device)
+    planes = [(split3_planes(w)[2].view(torch.int32) >> 16).to(torch.int16)[ch, k] for w in (m1, w1s)]
+    return torch.stack(planes).contiguous()
+
+
+_LO_TABLES: dict = {}            # (m1 ptr, version, w1s ptr, version) -> (m1, w1s, table): the table of bare tensors, built once
+
+
+def _fold_lo_cached(m1: torch.Tensor, w1s: torch.Tensor) -> torch.Tensor:
+    key = (m1.data_ptr(), m1._version, w1s.data_ptr(), w1s._version)
+    hit = _LO_TABLES.get(key)
+    if hit is None:
+        # Entries are dropped only while no stream is capturing, oldest first, and never the one in use.  A graph captured with bare
+        # tensors holds the table's ADDRESS, not the tensor: a caller that replays such a graph after 64 other weight pairs have
+        # passed through here must pass the table itself (folded[3]), as the model's cache does.
+        if len(_LO_TABLES) >= 64 and not torch.cuda.is_current_stream_capturing():
+            _LO_TABLES.pop(next(iter(_LO_TABLES)))
+        hit = (m1, w1s, fold_lo_table(m1, w1s))      # (the operands are held: their addresses cannot be reused under the key)
+        _LO_TABLES[key] = hit
+    return hit[2]
+
+
 def gcn_layer_cls_fold_fwd(graph: Graph, batch: int, x: torch.Tensor, folded, residual: bool, packed: dict, sigmoid: bool = False,
                            kidsum_in: Optional[torch.Tensor] = None) -> torch.Tensor:
     """gcn_layer_cls_fwd for a last layer without ReLU and without jk_in, from ``folded`` = (m1, w1s, c1) of
     nn._heads.fold_last_into_heads (the layer's weight, scale and shift and the heads' w1, s1, t1 in one); ``residual``: the
-    layer adds its input.  Same logits to rounding; the layer's output tile is never formed (eg_gcn_layer_cls_fold_fwd)."""
+    layer adds its input.  Same logits to rounding; the layer's output tile is never formed.  The products run on the bf16 matrix
+    path from exact splits (eg_gcn_layer_cls_fold_split_fwd; a handle created under EG_LAYER_SPLIT=0 runs the fp32 body of
+    eg_gcn_layer_cls_fold_fwd); ``folded`` may carry the lo-plane table of fold_lo_table as a fourth element, otherwise it is built
+    here once per (address, version) of m1 and w1s."""
     rows = graph.num_nodes * batch
-    m1, w1s, c1 = folded
+    m1, w1s, c1 = folded[:3]
+    lo = folded[3] if len(folded) > 3 else _fold_lo_cached(m1, w1s)      # (the model's cache brings the table along)
     _check_rows(x, "x", rows)
     _check(m1, "m1", (C, C))
     _check(w1s, "w1s", (C, C))
     _check(c1, "c1", numel=C)
     _check_rows(kidsum_in, "kidsum_in", graph.kidsum_rows * batch, optional=True)
     out = torch.empty((graph.num_nodes - graph.num_conn) * batch, 4, dtype=torch.float32, device=x.device)
-    call("eg_gcn_layer_cls_fold_fwd", graph._h, batch, x, bool(residual), kidsum_in, m1, w1s, c1,
+    _check(lo, "lo planes", (2, 4, 4, 2, 4, 16, 8), dtype=torch.int16)
+    call("eg_gcn_layer_cls_fold_split_fwd", graph._h, batch, x, bool(residual), kidsum_in, m1, w1s, c1, lo,
          *[packed[k] for k in _HEAD_KEYS[3:]], sigmoid, out)
     return out
 

@@ -100,8 +100,8 @@ extern "C" {
  * 149: eg_embed_workspace_bytes, eg_embed_block_fwd, eg_embed_conv_fwd, eg_embed_act_fwd, eg_embed_act_bwd, eg_embed_res_bwd_input.
  * 150: eg_pyramid_block_fwd, eg_pyramid_block_scratch_bytes.
  * 151: eg_pyramid_train_workspace_bytes, eg_pyramid_conv_fwd, eg_pyramid_act_fwd, eg_pyramid_act_bwd, eg_pyramid_conv_bwd_data,
- * eg_pyramid_conv_bwd_weight. */
-#define EG_ABI_VERSION 151
+ * eg_pyramid_conv_bwd_weight.  152: eg_gcn_layer_cls_fold_split_fwd. */
+#define EG_ABI_VERSION 152
 
 #define EG_CHANNELS 128 /* node_embedding_dim == node_hidden_dim (configs/default.yml:13-14) */
 
@@ -236,6 +236,15 @@ int eg_gcn_layer_cls_fwd(const eg_graph* g, int batch, const float* x, const flo
 int eg_gcn_layer_cls_fold_fwd(const eg_graph* g, int batch, const float* x, int residual, const float* kidsum_in, const float* m1,
                               const float* w1s, const float* c1, const float* w2, const float* s2, const float* t2, const float* w3,
                               const float* b3, int sigmoid, float* logits, eg_stream_t stream);
+/* eg_gcn_layer_cls_fold_fwd with the two products on the bf16 matrix path (exact 3-piece splits of both operands, six piece
+ * products, fp32-accurate: as the plain layer's split chain).  lo_planes: the lowest bf16 piece of every element of m1 and w1s,
+ * 64 KB, 16-byte aligned, in the order the kernel's lanes fetch it -- [matrix 2][k-step 4][wave 4][column block 2][kq 4][i 16][e 8]
+ * = lo(Wm[32 wave + 16 cb + i][koff(kq) + 8 step + e]), koff = {0, 64, 32, 96} (echoglad_amd/ops/infer.py fold_lo_table builds
+ * it; with residual = 0 the second matrix' half is not read).  A handle created under EG_LAYER_SPLIT=0 runs the fp32 body of
+ * eg_gcn_layer_cls_fold_fwd instead.  Everything else as there. */
+int eg_gcn_layer_cls_fold_split_fwd(const eg_graph* g, int batch, const float* x, int residual, const float* kidsum_in, const float* m1,
+                                    const float* w1s, const float* c1, const void* lo_planes, const float* w2, const float* s2,
+                                    const float* t2, const float* w3, const float* b3, int sigmoid, float* logits, eg_stream_t stream);
 
 /* JumpingKnowledge('max') of the reference (torch_geometric JumpingKnowledge as used at src/core/models.py:380-382,
  * :479-482: element-wise maximum over [node features, h_1, .., h_L]) carried through the fused stack as a running maximum:

@@ -1,11 +1,14 @@
 """Lint over a kernel's assembly (hipcc -S --cuda-device-only): the operand-register rule of DESIGN_NOTES 5.14 for the bf16 chain of
-the split layer kernel (tile.h mfma_rowblock_bf16x6).  Walks one function straight through and reports every vector-ALU or
-LDS-return write to a register that an earlier v_mfma read as its A / B operand with no guard (`s_nop 15`, which in that kernel
+the split layer kernel (tile.h mfma_rowblock_bf16x6) and of the folded last layer's bf16 body (v_mfma_f32_16x16x32_bf16, tile.h
+fs_step; gcn_layer_ps_fold_split.hip).  Walks one function straight through and reports every vector-ALU, LDS-return or
+vector-memory-return write (global_load / buffer_load / scratch_load destinations: the streamed lo fragments land in operand
+registers) to a register that an earlier bf16 v_mfma read as its A / B operand with no guard (`s_nop 15`, which in these kernels
 only the guard emits, behind its accumulator read) in between.  Straight-line only: the tile loop's back edge is covered by the
-guard that ends every row block.
+guard that ends every chain.
 usage: hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -amdgpu-atomic-optimizer-strategy=None --cuda-device-only -S \\
            echoglad_amd/csrc/gcn_layer_ps_split.hip -o /tmp/split.s && python tools/check_mfma_operands.py /tmp/split.s [function substring]
-Exit code 1 if anything is found.  (Shipped form: 96 MFMAs, 16 guards, 0 findings per split instantiation.)"""
+Exit code 1 if anything is found.  (Shipped form: 96 MFMAs, 16 guards, 0 findings per split instantiation; 384 MFMAs and 32 guards for the folded body with the
+residual, 192 and 16 without.)"""
 import re
 import sys
 
@@ -43,12 +46,12 @@ def check(lines):
         if not m:
             continue
         op, toks = m.group(1), [t.strip() for t in m.group(2).split(",")]
-        if op.startswith("v_mfma_f32_32x32x16_bf16"):
+        if op.startswith(("v_mfma_f32_32x32x16_bf16", "v_mfma_f32_16x16x32_bf16")):
             mfmas += 1
             for t in toks[1:3]:
                 for r in regs(t):
                     last_read[r] = (i, guards)
-        elif (op.startswith("v_") and not op.startswith(("v_cmp", "v_readfirstlane", "v_readlane", "v_nop", "v_mfma"))) or op.startswith("ds_read"):
+        elif (op.startswith("v_") and not op.startswith(("v_cmp", "v_readfirstlane", "v_readlane", "v_nop", "v_mfma"))) or op.startswith(("ds_read", "global_load", "buffer_load", "scratch_load")):
             for r in regs(toks[0]):
                 if r in last_read:
                     j, g = last_read.pop(r)

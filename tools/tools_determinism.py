@@ -1,6 +1,7 @@
 """Diagnostic: soak test for launch-to-launch determinism of the fused layer kernels at FULL grid size (the register-reuse
 hazard of DESIGN.md section 5 item 14 only showed with every CU busy).  Runs each form `reps` times and compares bits; then a whole training step `reps / 10` times.
-usage (GPU box, repo root): python3 tools/tools_determinism.py [reps]"""
+usage (GPU box, repo root): python3 tools/tools_determinism.py [reps]
+                            python3 tools/tools_determinism.py [reps] fold     the same forms for the folded last layer + heads only"""
 import os
 import sys
 
@@ -38,6 +39,35 @@ def soak(frame, naux, B, mode, reps, main_only=False, diag=False, conn=False):
             bad += 1
     print(f"{frame}x{frame} naux={naux} main_only={main_only} diagonal={diag} connection_nodes={conn} B={B} {mode}: {bad} of {reps - 1} "
           "launches differ from the first", flush=True)
+    return bad
+
+
+def soak_fold(frame, naux, B, reps, main_only=False, diag=False, conn=False):
+    """The chained pair of soak() with the folded last layer + heads (eg_gcn_layer_cls_fold_split_fwd: the bf16 body unless the
+    handle was created under EG_LAYER_SPLIT=0) as its second launch; compared on the device, one read-back at the end."""
+    from echoglad_amd.nn._heads import fold_last_into_heads
+    g = ops.Graph.topo(frame, naux, main_only, diag_main=diag, diag_aux=diag and not main_only, use_connection_nodes=conn)
+    n = g.num_nodes
+    x = synthetic_node_feats(B * n, 128, seed=1).to(DEV)
+    w = (synthetic_node_feats(128, 128, seed=2) * 0.1).to(DEV)
+    sc, sh = torch.ones(128, device=DEV), torch.zeros(128, device=DEV)
+    f = lambda *shape: (synthetic_node_feats(int(torch.tensor(shape).prod()), 1, 7).reshape(shape) * 0.1).to(DEV).contiguous()
+    packed = {"w1": f(128, 128), "s1": f(128) + 1, "t1": f(128), "w2": f(4, 16, 32), "s2": f(64) + 1, "t2": f(64), "w3": f(4, 16), "b3": f(4)}
+    fold = fold_last_into_heads(w, sc, sh, packed["w1"], packed["s1"], packed["t1"], True)
+    fold = fold + (ops.fold_lo_table(fold[0], fold[1]),)
+    chained = g.kidsum_rows > 0
+    ka = ops.new_kidsum(g, B) if chained else None
+    first, bad = None, torch.zeros((), dtype=torch.int64, device=DEV)
+    for _ in range(reps):
+        h = ops.gcn_layer_fwd(g, B, x, w, sc, sh, x, relu=True, kidsum_out=ka)
+        out = ops.gcn_layer_cls_fold_fwd(g, B, h, fold, True, packed, kidsum_in=ka)
+        if first is None:
+            first = out.clone()
+        else:
+            bad += (out != first).any()
+    bad = int(bad)
+    print(f"folded last layer + heads {frame}x{frame} naux={naux} main_only={main_only} diagonal={diag} connection_nodes={conn} B={B}: "
+          f"{bad} of {reps - 1} chained launch pairs differ from the first", flush=True)
     return bad
 
 
@@ -129,6 +159,12 @@ def soak_graphed(replays, runs=3):
 if __name__ == "__main__":
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 200
     total = 0
+    if "fold" in sys.argv[2:]:          # (the lengths of DESIGN_NOTES 9.8: reps = 9000)
+        total += soak_fold(224, 7, 8, reps)
+        for kw in ({"main_only": True}, {"diag": True}, {"conn": True}):
+            total += soak_fold(224, 7, 32 if "main_only" in kw else 8, max(reps * 2 // 9, 2), **kw)
+        total += soak_fold(448, 8, 8, max(reps // 18, 2))
+        sys.exit(1 if total else 0)
     for mode in ("f32",):
         total += soak(224, 7, 8, mode, reps)
         total += soak(224, 7, 32, mode, reps, main_only=True)
