@@ -8,7 +8,8 @@ modules (MIOpen); ``enable_hip_frontend()`` switches its eval-mode forward to th
 HIP path that is always on begins at the tail of ``create_node_pixels``, where the reference applies a 1x1 convolution + ReLU to
 every decoder map and concatenates the permuted maps per sample in a Python loop (models.py:707-756).  That tail is ONE launch
 here (``pack_node_features_linear`` -> eg_conv1x1_relu_pack_levels) and writes the GNN's input layout directly; everything
-after it is the base class's ``forward_nodes``.
+after it is the base class's ``forward_nodes``.  Its backward goes through torch's convolution gradients by default and, with
+``enable_hip_frontend(..., tail=True)``, through the fixed-order eg_conv1x1_relu_pack_bwd.
 
 Module names (``down_convs.{i}.conv1 / BN1 / conv2 / BN2``, ``up_convs.{i}.*``, ``linears.{i}``) are the reference's, so a
 reference checkpoint of this variant loads with ``strict=True`` (src/core/checkpointers.py:94-98)."""
@@ -76,14 +77,23 @@ class UNetNodeFeatureModel(HierarchicalPatchModel):
         self.linears = nn.ModuleList(nn.Conv2d(c, self.node_embedding_dim, kernel_size=1) for c in feats_in)
         self.hip_frontend = False           # plain attributes: no parameter, no buffer, not in the state_dict
         self.hip_frontend_train = False
+        self.hip_tail = False
 
-    def enable_hip_frontend(self, flag: bool = True, train: bool = False) -> "UNetNodeFeatureModel":
+    def enable_hip_frontend(self, flag: bool = True, train: bool = False, tail: bool = False) -> "UNetNodeFeatureModel":
         """Opt in: in eval mode with autograd off, ``decoder_maps`` runs on the HIP front-end (``nn.unet_decoder_maps``: 35
         launches, bit-reproducible) instead of torch's modules.  Training and eval with gradients keep the torch path, unless
         ``train=True``: then training mode with autograd on takes ``nn.unet_decoder_maps_train`` (batch statistics, HIP backward,
-        bit-reproducible); eval with gradients stays on torch."""
+        bit-reproducible); eval with gradients stays on torch.  ``tail=True``, independent of ``train``: whenever autograd is on,
+        the tail (``linears`` + ReLU + packing) takes its fixed-order HIP backward (eg_conv1x1_relu_pack_bwd) instead of torch's
+        1 x 1 convolution gradients, the last piece of the step that was not reproducible bit for bit.  Not with
+        ``use_connection_nodes``: the connection-node means below still differentiate torch's 1 x 1 convolutions, so the step
+        would silently stay non-reproducible."""
+        if flag and tail and self.use_connection_nodes:
+            raise ValueError("enable_hip_frontend(tail=True) with use_connection_nodes=True: the connection-node means of "
+                             "create_node_pixels differentiate torch's 1 x 1 convolutions, the step would not be bit-reproducible")
         self.hip_frontend = bool(flag)
         self.hip_frontend_train = bool(flag) and bool(train)
+        self.hip_tail = bool(flag) and bool(tail)
         return self
 
     def decoder_maps(self, frames: torch.Tensor) -> List[torch.Tensor]:
@@ -114,7 +124,7 @@ class UNetNodeFeatureModel(HierarchicalPatchModel):
             # more, on the coarse maps only -- they are a few percent of the frame-sized one -- and on the frame-sized map's mean
             with torch.set_grad_enabled(torch.is_grad_enabled()):
                 conn = torch.stack([F.relu(m(f)).mean(dim=(2, 3)) for f, m in zip(feats, lin)], dim=1)        # [B, naux + 1, 128]
-        return self.pack_node_features_linear(feats, lin, B, node_coords, conn)
+        return self.pack_node_features_linear(feats, lin, B, node_coords, conn, backward="hip" if self.hip_tail else "torch")
 
 
 def reference_tail(model: UNetNodeFeatureModel, feats: List[torch.Tensor], B: int) -> torch.Tensor:

@@ -721,18 +721,20 @@ class HierarchicalPatchModel(nn.Module):
         feats = ops.pack_levels(maps, B, n, n_conn, out=self._static_node_feats(B, maps + [connection_embed]))
         return self._finish_node_features(feats, B, node_coords, connection_embed)
 
-    def pack_node_features_linear(self, features, linears, num_samples_per_batch: int, node_coords=None, connection_embed=None):
+    def pack_node_features_linear(self, features, linears, num_samples_per_batch: int, node_coords=None, connection_embed=None,
+                                  backward: str = "torch"):
         """The UNet variant's whole tail (models.py:707-756): ``F.relu(self.linears[i](features[i]))`` for every level (1x1
         convolutions to 128 channels) AND the node-major packing in one launch (eg_conv1x1_relu_pack_levels); the 128-channel
         NCHW maps are never formed.  ``features``: decoder maps coarse to fine [B, C_l, p_l, p_l] (the last one frame-sized),
         ``linears``: the matching ``nn.Conv2d(C_l, 128, kernel_size=1)`` modules.  Connection-node embeddings
-        [B, naux+1, 128] (means of the activated maps) come from the caller, as in ``pack_node_features``."""
+        [B, naux+1, 128] (means of the activated maps) come from the caller, as in ``pack_node_features``.  ``backward``: "torch" or
+        "hip" (ops.conv1x1_relu_pack_levels: the fixed-order HIP backward of the tail)."""
         B = int(num_samples_per_batch)
         n, n_conn = self._row_ranges()[:2]
         fl = [f.float() for f in features]
         ws, bs = [m.weight for m in linears], [m.bias for m in linears]
         feats = ops.conv1x1_relu_pack_levels(fl, ws, bs, B, n, n_conn,
-                                             out=self._static_node_feats(B, fl + ws + bs + [connection_embed]))
+                                             out=self._static_node_feats(B, fl + ws + bs + [connection_embed]), backward=backward)
         return self._finish_node_features(feats, B, node_coords, connection_embed)
 
     def forward(self, data_batch=None, x=None, node_coords=None, edge_index=None, node_type=None, batch_idx=None):

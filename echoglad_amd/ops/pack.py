@@ -1,5 +1,5 @@
 """Pooling and packing: the average-pool pyramid (pool.hip) and the node-feature packing of level maps, with or without the
-1 x 1 convolution in front (pack.hip)."""
+1 x 1 convolution in front (pack.hip; its fixed-order backward: pack_train.hip)."""
 from __future__ import annotations
 
 import ctypes as ct
@@ -7,7 +7,7 @@ from typing import Optional
 
 import torch
 
-from ._core import C, _check, _check_rows, _check_vec, call
+from ._core import C, _check, _check_rows, _check_vec, _scratch, call, raw
 
 
 def _addresses(tensors):
@@ -257,11 +257,58 @@ class _ConvReluPackFn(torch.autograd.Function):
         return (None, None, None, None, *gf, *gw, *gb)
 
 
+class _ConvReluPackHipFn(torch.autograd.Function):
+    """_ConvReluPackFn with the backward in HIP (eg_conv1x1_relu_pack_bwd: two launches, no atomics, a fixed order of summation,
+    so the gradients are bit-reproducible).  The node saves its own output rows: the ReLU's mask is read from them, the product is
+    not recomputed and no 128-channel NCHW map is formed."""
+
+    @staticmethod
+    def forward(ctx, batch, n_rows, row_offset, n_levels, *tensors):
+        feats = [t.contiguous() for t in tensors[:n_levels]]
+        feats = [f.clone() if _off16(f, int(f.shape[2])) else f for f in feats]          # what the backward reads is what is saved
+        weights = [t.contiguous() for t in tensors[n_levels:2 * n_levels]]
+        biases = list(tensors[2 * n_levels:3 * n_levels])
+        nodes = _alloc_nodes(batch, n_rows, row_offset, _rows_used(feats), feats[0].device)
+        _conv_pack_call(feats, weights, [b.contiguous() if b is not None else None for b in biases], nodes, batch, n_rows, row_offset)
+        ctx.meta = (batch, n_rows, row_offset, n_levels)
+        ctx.has_bias = [b is not None for b in biases]
+        ctx.save_for_backward(nodes, *feats, *weights)
+        return nodes
+
+    @staticmethod
+    def backward(ctx, d_nodes):
+        batch, n_rows, row_offset, n = ctx.meta
+        nodes, feats, weights = ctx.saved_tensors[0], ctx.saved_tensors[1:1 + n], ctx.saved_tensors[1 + n:]
+        need = ctx.needs_input_grad
+        dev = d_nodes.device
+        gf = [torch.empty_like(f) if need[4 + l] else None for l, f in enumerate(feats)]
+        gw = [torch.empty_like(w) if need[4 + n + l] else None for l, w in enumerate(weights)]
+        gb = [torch.empty(C, dtype=torch.float32, device=dev) if hb and need[4 + 2 * n + l] else None for l, hb in enumerate(ctx.has_bias)]
+        if all(g is None for g in gf + gw + gb):
+            return (None,) * (4 + 3 * n)
+        d_nodes = d_nodes.contiguous()
+        _check_rows(d_nodes, "d_nodes", batch * n_rows)
+        d_nodes = d_nodes.clone() if _off16(d_nodes) else d_nodes
+        nodes = nodes.clone() if _off16(nodes) else nodes
+        sides, chans = [int(f.shape[2]) for f in feats], [int(f.shape[1]) for f in feats]
+        side, chan = _ints(sides), _ints(chans)                  # (the gradients are fresh allocations: 16-byte aligned as they are)
+        ws = None
+        if any(g is not None for g in gw + gb):
+            ws = _scratch("tail_bwd", dev, int(raw("eg_conv1x1_relu_pack_bwd_workspace_bytes", chan, side, n, batch)))
+        call("eg_conv1x1_relu_pack_bwd", d_nodes, nodes, _addresses(feats), _addresses(weights), chan, side, n, batch, n_rows, row_offset,
+             ws, _addresses(gf), _addresses(gw), _addresses(gb))
+        return (None, None, None, None, *gf, *gw, *gb)
+
+
 def conv1x1_relu_pack_levels(feats, weights, biases, batch: int, n_rows: int, row_offset: int = 0,
-                             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                             out: Optional[torch.Tensor] = None, backward: str = "torch") -> torch.Tensor:
     """relu(Conv2d(C_l, 128, 1)(feats[l])) for every level (coarse to fine), written node-major [batch * n_rows, 128] like
     `pack_levels` (models.py:707-710 + :726-756 in one launch).  Differentiable w.r.t. features, weights and biases (not with
-    ``out=``: written in place)."""
+    ``out=``: written in place).  ``backward``: "torch" unpacks the node gradient to NCHW and lets torch differentiate the recomputed
+    relu(conv2d) of every level (MIOpen's weight gradient: not reproducible bit for bit); "hip" is eg_conv1x1_relu_pack_bwd, a
+    fixed-order backward in two launches."""
+    if backward not in ("torch", "hip"):
+        raise ValueError(f'backward must be "torch" or "hip", got {backward!r}')
     n = len(feats)
     if out is not None:
         feats = [f.contiguous() for f in feats]
@@ -270,4 +317,5 @@ def conv1x1_relu_pack_levels(feats, weights, biases, batch: int, n_rows: int, ro
         _pack_out(out, list(feats), int(batch), int(n_rows), int(row_offset), _rows_used(feats))
         _conv_pack_call(feats, weights, biases, out, int(batch), int(n_rows), int(row_offset))
         return out
-    return _ConvReluPackFn.apply(int(batch), int(n_rows), int(row_offset), n, *feats, *weights, *biases)
+    fn = _ConvReluPackHipFn if backward == "hip" else _ConvReluPackFn
+    return fn.apply(int(batch), int(n_rows), int(row_offset), n, *feats, *weights, *biases)

@@ -100,8 +100,9 @@ extern "C" {
  * 149: eg_embed_workspace_bytes, eg_embed_block_fwd, eg_embed_conv_fwd, eg_embed_act_fwd, eg_embed_act_bwd, eg_embed_res_bwd_input.
  * 150: eg_pyramid_block_fwd, eg_pyramid_block_scratch_bytes.
  * 151: eg_pyramid_train_workspace_bytes, eg_pyramid_conv_fwd, eg_pyramid_act_fwd, eg_pyramid_act_bwd, eg_pyramid_conv_bwd_data,
- * eg_pyramid_conv_bwd_weight.  152: eg_gcn_layer_cls_fold_split_fwd. */
-#define EG_ABI_VERSION 152
+ * eg_pyramid_conv_bwd_weight.  152: eg_gcn_layer_cls_fold_split_fwd.
+ * 153: eg_conv1x1_relu_pack_bwd_workspace_bytes, eg_conv1x1_relu_pack_bwd_plan, eg_conv1x1_relu_pack_bwd. */
+#define EG_ABI_VERSION 153
 
 #define EG_CHANNELS 128 /* node_embedding_dim == node_hidden_dim (configs/default.yml:13-14) */
 
@@ -922,6 +923,32 @@ int eg_unpack_levels(const float* nodes, float* const* level_maps, const int* le
 int eg_conv1x1_relu_pack_levels(const float* const* level_feats, const float* const* level_weights,
                                 const float* const* level_biases, const int* level_channels, const int* level_side,
                                 int n_levels, int batch, int64_t n_rows, int64_t row_offset, float* nodes, eg_stream_t stream);
+/* The backward of eg_conv1x1_relu_pack_levels (pack_train.hip): no atomics, a fixed order of summation, two launches on the
+ * caller's stream (products, then the sum over slices), no allocation, no synchronisation, no host read.
+ *   dz[b, pos, o] = d_nodes[row, o] where nodes[row, o] > 0, else 0 -- nodes is the FORWARD'S OUTPUT (relu(s) > 0 <=> s > 0, and a
+ *   pre-activation of exactly 0 gets gradient 0, as in torch): the product is not recomputed and the mask is the forward's own bits.
+ *   d_feats[l] [batch, c_l, side_l, side_l] = sum_o W[o, c] dz;  d_weights[l] [128, c_l] = sum_{b, pos} dz f;  d_biases[l] [128] =
+ *   sum_{b, pos} dz.  Each of the three arrays, and each entry, may be NULL: not wanted.  A level that wants nothing launches no
+ *   work; a call that wants nothing launches nothing.  level_feats[l] is read where d_weights[l] is wanted, level_weights[l] where
+ *   d_feats[l] is; workspace (eg_conv1x1_relu_pack_bwd_workspace_bytes) where a d_weights[l] or d_biases[l] is.
+ * The plan: a level's batch * ceil(side^2 / 64) tiles of 64 positions, numbered frame-major, are cut into slices of
+ *   tiles_per_slice = ceil(tiles / cap(c_l)) consecutive tiles, cap(c) = clamp(4096 / c, 16, 1024); slices = ceil(tiles /
+ *   tiles_per_slice), the last one may be short.  One workgroup per (level, slice, pass of 32 channels) sums its tiles in ascending
+ *   order, positions ascending; the slices are summed in 16 runs of ceil(slices / 16) consecutive slices, each ascending, then the
+ *   16 runs ascending.  The plan depends on (sides, channels, batch) alone, never on the device or the stream: the same inputs
+ *   give the same bits.  eg_conv1x1_relu_pack_bwd_plan is that arithmetic on the host (no device call), the one the launcher uses.
+ * Workspace: the sum over the levels of min(cap(c_l), tiles_l) * 128 * (c_l + 1) floats -- bounded whatever the batch: at most
+ *   2.62 MB per level up to 256 channels, 8 KiB * (c_l + 1) above; 19.9 MB for channels 512 .. 4 on sides 2 .. 128 and 224.
+ *   0 where the shapes are out of range (what eg_conv1x1_relu_pack_bwd refuses).
+ * EG_ERR_ARG before any launch, nothing written: as the forward (batch * n_rows >= 2^31, more than 16 levels, levels that do not
+ *   fit n_rows), and 16-byte operands elsewhere: d_nodes, nodes, and every level_feats[l] / d_feats[l] with side_l^2 % 4 == 0. */
+size_t eg_conv1x1_relu_pack_bwd_workspace_bytes(const int* level_channels, const int* level_side, int n_levels, int batch);
+int eg_conv1x1_relu_pack_bwd_plan(const int* level_channels, const int* level_side, int n_levels, int batch, int* level_slices,
+                                  int* level_tiles_per_slice);
+int eg_conv1x1_relu_pack_bwd(const float* d_nodes, const float* nodes, const float* const* level_feats,
+                             const float* const* level_weights, const int* level_channels, const int* level_side, int n_levels,
+                             int batch, int64_t n_rows, int64_t row_offset, void* workspace, float* const* d_feats,
+                             float* const* d_weights, float* const* d_biases, eg_stream_t stream);
 
 /* ---- average-pool pyramid of the frame embedding: the head of create_node_pixels (src/core/models.py:511-521) -------------
  * eg_avg_pool_pyramid_fwd: level_maps[l] [planes, side_l, side_l] = F.adaptive_avg_pool2d(x [planes, frame, frame], side_l)
