@@ -20,7 +20,7 @@ HEADER_PATH = _PKG.parent / "include" / "echoglad_hip.h"
 
 EG_OK, EG_ERR_ARG, EG_ERR_UNSUPPORTED, EG_ERR_HIP = 0, -1, -2, -3
 # EG_ABI_VERSION of the include/echoglad_hip.h that the structures below and the wrappers' argument order were written for
-ABI_VERSION = 153
+ABI_VERSION = 154
 
 _lib: Optional[ct.CDLL] = None
 

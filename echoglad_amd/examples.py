@@ -11,6 +11,10 @@ here (``pack_node_features_linear`` -> eg_conv1x1_relu_pack_levels) and writes t
 after it is the base class's ``forward_nodes``.  Its backward goes through torch's convolution gradients by default and, with
 ``enable_hip_frontend(..., tail=True)``, through the fixed-order eg_conv1x1_relu_pack_bwd.
 
+``UNetNoGNN`` / ``UNet`` are the reference's ablations without a GNN (``UNETIntermediateNoGnn`` / ``UNET``, models.py:759-838): the
+same front-end and tail, the node-type filter and the four heads; in eval mode everything behind the decoder is one launch
+(``ops.conv1x1_relu_heads`` -> eg_conv1x1_relu_heads_fwd).
+
 Module names (``down_convs.{i}.conv1 / BN1 / conv2 / BN2``, ``up_convs.{i}.*``, ``linears.{i}``) are the reference's, so a
 reference checkpoint of this variant loads with ``strict=True`` (src/core/checkpointers.py:94-98)."""
 from __future__ import annotations
@@ -21,6 +25,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import ops
 from .nn import C, HierarchicalPatchModel, unet_decoder_maps, unet_decoder_maps_train
 from .topology import get_topology
 
@@ -125,6 +130,46 @@ class UNetNodeFeatureModel(HierarchicalPatchModel):
             with torch.set_grad_enabled(torch.is_grad_enabled()):
                 conn = torch.stack([F.relu(m(f)).mean(dim=(2, 3)) for f, m in zip(feats, lin)], dim=1)        # [B, naux + 1, 128]
         return self.pack_node_features_linear(feats, lin, B, node_coords, conn, backward="hip" if self.hip_tail else "torch")
+
+
+class UNetNoGNN(UNetNodeFeatureModel):
+    """The reference's ablation ``UNETIntermediateNoGnn`` (src/core/models.py:759-799; ``unet_noGNN`` in its model registry): the
+    UNet's ``create_node_pixels``, the rows with ``node_type != 0`` dropped, the four classifier heads -- no GNN layer in between.
+    Constructor and state_dict keys are ``UNetNodeFeatureModel``'s (the reference's ablations construct the unused ``gnn_layers``
+    too), so a reference checkpoint loads with ``strict=True``; ``gnn_layers`` never receive a gradient.
+
+    In eval mode with autograd off the whole path behind the decoder is ONE launch (``ops.conv1x1_relu_heads``): the tail's
+    128-channel rows go from LDS into the heads and are never written, and the rows the filter drops are never computed -- the
+    bilinear samples of the coordinate nodes and the connection-node means, which the reference computes and then discards, are
+    skipped.  Same logits, bit for bit, as the composed route ``forward_heads(create_node_pixels(...))`` that every other mode
+    takes (and this one with ``fuse_tail = False``).  ``edge_index`` is accepted and never read: no graph handle is resolved."""
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        self.fuse_tail = True               # plain attribute, like hip_frontend
+
+    def forward(self, data_batch=None, x=None, node_coords=None, edge_index=None, node_type=None, batch_idx=None):
+        if data_batch is not None:
+            x = data_batch.x
+            if self.use_coordinate_graph:
+                node_coords = data_batch.node_coords
+        B = x.shape[0]
+        if self.fuse_tail and not self.training and not torch.is_grad_enabled() and not self._narrow:
+            feats, lin = self.decoder_maps(x), list(self.linears)
+            if self.use_main_graph_only:
+                feats, lin = feats[-1:], lin[-1:]
+            rows, n_valid = sum(int(f.shape[2]) * int(f.shape[3]) for f in feats), self._row_ranges()[2]
+            if rows != n_valid:
+                raise RuntimeError(f"the decoder's levels give {rows} rows per frame, the topology has {n_valid} valid nodes")
+            out = ops.conv1x1_relu_heads([f.float() for f in feats], [m.weight for m in lin], [m.bias for m in lin], B,
+                                         self._packed_classifier(), sigmoid=self.output_activation == "sigmoid")
+            return out.squeeze(1), None
+        nc = node_coords.reshape(B, 4, -1) if self.use_coordinate_graph else None
+        return self.forward_heads(self.create_node_pixels(x, B, nc), B).squeeze(1), None
+
+
+class UNet(UNetNoGNN):
+    """The reference's ``UNET`` (src/core/models.py:802-838; ``unet`` in its registry): the same forward under its second name."""
 
 
 def reference_tail(model: UNetNodeFeatureModel, feats: List[torch.Tensor], B: int) -> torch.Tensor:

@@ -369,6 +369,24 @@ class HierarchicalPatchModel(nn.Module):
             return self._forward_train(node_feats, graph, gb, B, node_coords)
         return self._forward_stepwise(node_feats, graph, gb, B, node_coords)
 
+    def forward_heads(self, node_feats: torch.Tensor, batch: int) -> torch.Tensor:
+        """The last step of ``forward_nodes`` with no layer in front of it: node_feats [B*N, 128] -> the node-type filter (a row
+        range per frame) and the four heads -> logits [B*N_valid, n_out].  What the reference's no-GNN baselines run behind
+        ``create_node_pixels`` (models.py:791-797).  The heads' existing routes: eg_classifier_fwd in eval mode where nothing wants
+        a gradient, the stacked heads node in training mode, the torch modules where neither applies (narrow widths, eval mode
+        with gradients, frozen sub-modules)."""
+        n, n_conn, n_valid, _, _ = self._row_ranges()
+        B = int(batch)
+        if node_feats.shape[0] != B * n:
+            raise RuntimeError(f"{node_feats.shape[0]} node rows is not {B} frames of {n} nodes")
+        h = node_feats.contiguous()
+        wants_grad = torch.is_grad_enabled() and (h.requires_grad or any(p.requires_grad for p in self.node_classifiers.parameters()))
+        if not self.training and not wants_grad and not self._narrow:
+            return ops.classifier_fwd(h, B, n, n_conn, n_valid, self._packed_classifier(), sigmoid=self.output_activation == "sigmoid")
+        if self.training and self._stacked_heads_ok():
+            return self._classifier_train(h, B, n, n_conn, n_valid)
+        return self._classifier_modules(h, B, n, n_conn, n_valid)
+
     # ---- eval: folded layers, one launch each ---------------------------------------------------------------------------------
     def _forward_eval_fused(self, x0: torch.Tensor, graph: ops.Graph, gb: int, B: int, node_coords, jk_fused: bool):
         n, n_conn, n_valid, _, _ = self._row_ranges()

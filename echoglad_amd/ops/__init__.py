@@ -8,7 +8,7 @@ One module per family of entry points; ``_core`` holds what they share (the call
 the scratch cache).  Everything public is re-exported here: ``from echoglad_amd import ops; ops.gcn_layer_fwd(...)``."""
 from ._core import C, _level_arrays, _ptr, _stream                                         # noqa: F401  (_*: tests' raw ABI calls)
 from .graph import LAUNCH_KINDS, Graph, dropout_epoch, dropout_epoch_add, dropout_epoch_set, edge_hash, layer_timing   # noqa: F401
-from .infer import classifier_fwd, fold_lo_index, fold_lo_table, gcn_aggregate, gcn_layer_cls_fold_fwd, gcn_layer_cls_fwd, gcn_layer_fwd, linear128_fwd, new_kidsum, split3_planes          # noqa: F401
+from .infer import classifier_fwd, conv1x1_relu_heads, fold_lo_index, fold_lo_table, gcn_aggregate, gcn_layer_cls_fold_fwd, gcn_layer_cls_fwd, gcn_layer_fwd, linear128_fwd, new_kidsum, split3_planes          # noqa: F401
 from .train import (CLS_GRADS_FLOATS, bn_act_bwd, bn_act_fwd, bn_act_fwd_tiles, bn_stats, classifier_bwd,             # noqa: F401
                     classifier_layer_sums_supported, classifier_recompute_h_supported, classifier_train_fwd,
                     classifier_train_fwd_act, colsum128, dweight128, gcn_layer_bwd, gcn_layer_train_fwd, lower_sums_supported)

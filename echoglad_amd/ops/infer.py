@@ -8,6 +8,7 @@ import torch
 
 from ._core import C, _check, _check_rows, _check_vec, call
 from .graph import Graph
+from .pack import _addresses, _conv_levels, _ints
 
 _HEAD_KEYS = ("w1", "s1", "t1", "w2", "s2", "t2", "w3", "b3")       # the packed inference parameters of the 4 heads, in call order
 
@@ -180,4 +181,25 @@ def classifier_fwd(h: torch.Tensor, batch: int, n_per_frame: int, row_lo: int, n
     _check_rows(h, "h", batch * n_per_frame)
     out = torch.empty(batch * n_valid, 4, dtype=torch.float32, device=h.device)
     call("eg_classifier_fwd", h, batch, n_per_frame, row_lo, n_valid, *[packed[k] for k in _HEAD_KEYS], sigmoid, out)
+    return out
+
+
+_HEAD_SHAPES = {"w1": (C, C), "s1": (C,), "t1": (C,), "w2": (4, 16, 32), "s2": (64,), "t2": (64,), "w3": (4, 16), "b3": (4,)}
+
+
+def conv1x1_relu_heads(feats, weights, biases, batch: int, packed: dict, sigmoid: bool = False) -> torch.Tensor:
+    """``classifier_fwd(conv1x1_relu_pack_levels(feats, weights, biases, batch, sum p_l^2), ...)`` in ONE launch
+    (eg_conv1x1_relu_heads_fwd), bit for bit: relu(Conv2d(C_l, 128, 1)(feats[l])) of every level (coarse to fine) goes from LDS
+    straight into the 4 heads, the node-major [batch * N, 128] rows are never written.  -> logits [batch * sum p_l^2, 4]; row
+    b * sum + sum_{k<l} p_k^2 + pos is position pos of level l of frame b.  Inference only: nothing here is differentiable."""
+    batch = int(batch)
+    feats = [f.detach().contiguous() for f in feats]
+    weights = [w.detach().contiguous() for w in weights]
+    biases = [b.detach().contiguous() if b is not None else None for b in biases]
+    feats, biases, chans, sides = _conv_levels(feats, weights, biases, batch)
+    for k in _HEAD_KEYS:
+        _check(packed[k], k, _HEAD_SHAPES[k])
+    out = torch.empty(batch * sum(p * p for p in sides), 4, dtype=torch.float32, device=feats[0].device)
+    call("eg_conv1x1_relu_heads_fwd", _addresses(feats), _addresses(weights), _addresses(biases), _ints(chans), _ints(sides), len(feats),
+         batch, *[packed[k] for k in _HEAD_KEYS], bool(sigmoid), out)
     return out

@@ -192,7 +192,9 @@ def pack_levels(maps, batch: int, n_rows: int, row_offset: int = 0, out: Optiona
     return _PackLevelsFn.apply(int(batch), int(n_rows), int(row_offset), *maps)
 
 
-def _conv_pack_call(feats, weights, biases, nodes, batch, n_rows, row_offset):
+def _conv_levels(feats, weights, biases, batch):
+    """The level arguments of the 1 x 1 convolution entry points, checked: (features, biases) with the operands that would reach a
+    16-byte access off its alignment copied, the channel counts and the sides."""
     n = len(feats)
     if len(weights) != n or len(biases) != n:
         raise RuntimeError("1..16 levels, one weight and one bias (or None) per level")
@@ -205,9 +207,14 @@ def _conv_pack_call(feats, weights, biases, nodes, batch, n_rows, row_offset):
         _check_vec(b, "level bias", C)
     feats = [f.clone() if _off16(f, p) else f for f, p in zip(feats, sides)]
     biases = [b.clone() if _off16(b) else b for b in biases]
+    return feats, biases, chans, sides
+
+
+def _conv_pack_call(feats, weights, biases, nodes, batch, n_rows, row_offset):
+    feats, biases, chans, sides = _conv_levels(feats, weights, biases, batch)
     at = nodes.clone() if _off16(nodes) else nodes
-    call("eg_conv1x1_relu_pack_levels", _addresses(feats), _addresses(weights), _addresses(biases), _ints(chans), _ints(sides), n, batch,
-         n_rows, row_offset, at)
+    call("eg_conv1x1_relu_pack_levels", _addresses(feats), _addresses(weights), _addresses(biases), _ints(chans), _ints(sides), len(feats),
+         batch, n_rows, row_offset, at)
     if at is not nodes:
         nodes.copy_(at)
 

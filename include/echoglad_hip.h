@@ -101,8 +101,9 @@ extern "C" {
  * 150: eg_pyramid_block_fwd, eg_pyramid_block_scratch_bytes.
  * 151: eg_pyramid_train_workspace_bytes, eg_pyramid_conv_fwd, eg_pyramid_act_fwd, eg_pyramid_act_bwd, eg_pyramid_conv_bwd_data,
  * eg_pyramid_conv_bwd_weight.  152: eg_gcn_layer_cls_fold_split_fwd.
- * 153: eg_conv1x1_relu_pack_bwd_workspace_bytes, eg_conv1x1_relu_pack_bwd_plan, eg_conv1x1_relu_pack_bwd. */
-#define EG_ABI_VERSION 153
+ * 153: eg_conv1x1_relu_pack_bwd_workspace_bytes, eg_conv1x1_relu_pack_bwd_plan, eg_conv1x1_relu_pack_bwd.
+ * 154: eg_conv1x1_relu_heads_fwd. */
+#define EG_ABI_VERSION 154
 
 #define EG_CHANNELS 128 /* node_embedding_dim == node_hidden_dim (configs/default.yml:13-14) */
 
@@ -949,6 +950,19 @@ int eg_conv1x1_relu_pack_bwd(const float* d_nodes, const float* nodes, const flo
                              const float* const* level_weights, const int* level_channels, const int* level_side, int n_levels,
                              int batch, int64_t n_rows, int64_t row_offset, void* workspace, float* const* d_feats,
                              float* const* d_weights, float* const* d_biases, eg_stream_t stream);
+/* The no-GNN baselines (src/core/models.py:759-838: create_node_pixels, h[node_type == 0], the 4 heads) behind the decoder in ONE
+ * launch (tail_heads.hip): eg_classifier_fwd(eg_conv1x1_relu_pack_levels(...)) without the node-major rows in between, bit for bit
+ * -- the tail keeps k_conv1x1_relu_pack's order of summation, the heads are k_classifier's body.  The level arguments as
+ * eg_conv1x1_relu_pack_levels, the head arguments as eg_classifier_fwd (eval-mode BatchNorm folded into s* / t*).
+ * logits [batch * sum_l side_l^2, 4]: row b * sum + sum_{k<l} side_k^2 + pos is position pos of level l of frame b.  The rows the
+ * node-type filter drops (connection rows in front of the levels, coordinate rows behind them) are never computed: no row_lo.
+ * No allocation, no synchronisation, no atomics; capturable.  EG_ERR_ARG before any launch: NULL pointers, n_levels outside 1..16,
+ * batch < 1, a side or channel count < 1, batch * sum_l side_l^2 >= 2^31, and logits, a bias or a level map with side_l^2 % 4 == 0
+ * that is not 16-byte aligned. */
+int eg_conv1x1_relu_heads_fwd(const float* const* level_feats, const float* const* level_weights,
+                              const float* const* level_biases, const int* level_channels, const int* level_side, int n_levels,
+                              int batch, const float* w1, const float* s1, const float* t1, const float* w2, const float* s2,
+                              const float* t2, const float* w3, const float* b3, int sigmoid, float* logits, eg_stream_t stream);
 
 /* ---- average-pool pyramid of the frame embedding: the head of create_node_pixels (src/core/models.py:511-521) -------------
  * eg_avg_pool_pyramid_fwd: level_maps[l] [planes, side_l, side_l] = F.adaptive_avg_pool2d(x [planes, frame, frame], side_l)
