@@ -1,6 +1,7 @@
 """-m gpu: the device-side balanced-accuracy evaluator (csrc/metrics.hip) -- counts and scores against the reference's recorded
 numbers, inside engine.eval_step next to the landmark evaluator, captured into a HIP graph, past its capacity, and its argument
-checks."""
+checks.  Every input here fits one sweep of the capped grid (at most 106 workgroups); the shapes past the cap, every channel
+count and the merge's strides are in tests/test_gpu_counts_sweeps.py."""
 import os
 
 import numpy as np
