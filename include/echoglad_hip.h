@@ -102,8 +102,9 @@ extern "C" {
  * 151: eg_pyramid_train_workspace_bytes, eg_pyramid_conv_fwd, eg_pyramid_act_fwd, eg_pyramid_act_bwd, eg_pyramid_conv_bwd_data,
  * eg_pyramid_conv_bwd_weight.  152: eg_gcn_layer_cls_fold_split_fwd.
  * 153: eg_conv1x1_relu_pack_bwd_workspace_bytes, eg_conv1x1_relu_pack_bwd_plan, eg_conv1x1_relu_pack_bwd.
- * 154: eg_conv1x1_relu_heads_fwd. */
-#define EG_ABI_VERSION 154
+ * 154: eg_conv1x1_relu_heads_fwd.
+ * 155: eg_sgd_step, eg_rmsprop_step. */
+#define EG_ABI_VERSION 155
 
 #define EG_CHANNELS 128 /* node_embedding_dim == node_hidden_dim (configs/default.yml:13-14) */
 
@@ -558,6 +559,44 @@ typedef struct eg_adam_tensor {
 } eg_adam_tensor;
 int eg_adam_step(const eg_adam_tensor* tensors, int count, float* steps, float lr, const float* lr_device, float beta1, float beta2, float eps, float weight_decay,
                  int maximize, eg_stream_t stream);
+
+/* ---- the reference's other two optimizer names (src/builders/optimizer_builder.py: sgd, rmsprop), each ONE launch like eg_adam_step:
+ * a HOST array of `count` entries of device pointers that travels in the kernel arguments, steps [count] device floats (the number of
+ * updates of each tensor so far, advanced by the launch), lr / lr_device as in eg_adam_step.  Every argument check comes before the
+ * first HIP call.  EG_ERR_UNSUPPORTED (nothing launched) for count > EG_SGD_MAX_TENSORS / EG_RMSPROP_MAX_TENSORS: split the list.
+ * eg_sgd_step -- torch.optim.SGD (_single_tensor_sgd's order):
+ *   g = grad (maximize: -grad) + weight_decay * p
+ *   momentum != 0:  buf = steps[k] == 0 ? g : momentum * buf + (1 - dampening) * g;   g = nesterov ? g + momentum * buf : buf
+ *   p -= lr * g;   then steps[k] += 1
+ * The first update of a tensor copies g into the buffer; the kernel reads that from the DEVICE count, so the arguments of the launch
+ * are the same in every step.  momentum == 0: momentum_buffer may be NULL and is not touched; otherwise it must not be NULL.
+ * EG_ERR_ARG: nesterov with momentum <= 0 or dampening != 0, momentum < 0, weight_decay < 0 (torch's constructor checks).
+ * eg_rmsprop_step -- torch.optim.RMSprop (_single_tensor_rmsprop's order):
+ *   g as above;  sq = alpha * sq + (1 - alpha) * g * g
+ *   centered:  ga += (1 - alpha) * (g - ga);  avg = sqrt(sq - ga * ga) + eps          else:  avg = sqrt(sq) + eps
+ *   momentum > 0:  buf = momentum * buf + g / avg;  p -= lr * buf                     else:  p -= lr * g / avg;   then steps[k] += 1
+ * grad_avg non-NULL exactly when centered, momentum_buffer non-NULL exactly when momentum > 0, else EG_ERR_ARG; EG_ERR_ARG as well
+ * for alpha, eps, momentum or weight_decay < 0. */
+#define EG_SGD_MAX_TENSORS 120
+#define EG_RMSPROP_MAX_TENSORS 84
+typedef struct eg_sgd_tensor {
+    float* param;
+    const float* grad;
+    float* momentum_buffer; /* nullable (momentum == 0) */
+    int64_t numel;
+} eg_sgd_tensor;
+typedef struct eg_rmsprop_tensor {
+    float* param;
+    const float* grad;
+    float* square_avg;
+    float* grad_avg;        /* non-NULL iff centered */
+    float* momentum_buffer; /* non-NULL iff momentum > 0 */
+    int64_t numel;
+} eg_rmsprop_tensor;
+int eg_sgd_step(const eg_sgd_tensor* tensors, int count, float* steps, float lr, const float* lr_device, float momentum, float dampening,
+                float weight_decay, int nesterov, int maximize, eg_stream_t stream);
+int eg_rmsprop_step(const eg_rmsprop_tensor* tensors, int count, float* steps, float lr, const float* lr_device, float alpha, float eps,
+                    float weight_decay, float momentum, int centered, int maximize, eg_stream_t stream);
 
 /* ---- losses on the logits and landmark decode (the steps right after the hot path) ---------------------
  * Reference: src/core/criterion.py:13-27 (WeightedBCEWithLogitsLoss), :93-151 (ExpectedLandmarkMSE),
