@@ -21,6 +21,17 @@ constexpr int PS_THREADS = 512;
 constexpr int PS_LDS_DIS = 4 * TILE * LDA + 16 + 64;  // float offsets inside the dynamic LDS block (tile-id ring, CLS counter, descriptor ring)
 constexpr int PS_LDS_PAT = PS_LDS_DIS + 2 * TILE;
 
+// FSPLIT, FOLD = 1: of a tile's four 16-row blocks, the first EG_FOLD_PROD_RB get their residual product c + h W1s^T from the
+// producer waves (DESIGN_NOTES 9.10 holds the measurements the value was chosen by)
+#ifndef EG_FOLD_PROD_RB
+#define EG_FOLD_PROD_RB 4
+#endif
+static_assert(EG_FOLD_PROD_RB >= 2 && EG_FOLD_PROD_RB <= 4, "2, 3 or 4 row blocks");
+// ... and the priority the producer waves run that product at (they load at 3; an experiment flag, DESIGN_NOTES 9.10)
+#ifndef EG_FOLD_PROD_PRIO
+#define EG_FOLD_PROD_PRIO 3
+#endif
+
 struct PsDims {
     int n_per_frame, batch, tiles_per_frame, relu, transpose_w, has_res;
     int kid_rows;      // rows per frame of the child-sum side buffers (kin / kout)
@@ -55,8 +66,15 @@ __device__ inline int ps_static_tile(int ord, int n_tiles) {
 #define PSTAMP(i) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long _t = __builtin_amdgcn_s_memtime(); \
                        __builtin_amdgcn_s_waitcnt(0xC07F); st[i] += _t - t_prev; t_prev = _t; __builtin_amdgcn_sched_barrier(0); } while (0)
 #define PSTAMP_INIT unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long t_prev = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F)
+// -DEG_STAMP_PROD: the producers report their stamps 4..7 instead of 0..3 -- FSPLIT, FOLD = 1: the wait at the first meeting,
+// the product, the wait at the second meeting, the partial write -- in the same four places (eg_debug_phase_cycles hands out 11 values)
+#ifdef EG_STAMP_PROD
+#define PSTAMP_PROD_FIRST 4
+#else
+#define PSTAMP_PROD_FIRST 0
+#endif
 #define PSTAMP_FLUSH(base) do { if (lane_k == 0) { unsigned long long* stats = reinterpret_cast<unsigned long long*>(counters + WALK_GROUPS * WALK_CTR_STRIDE); \
-                                for (int i = 0; i < 4; ++i) atomicAdd(&stats[(base) + i], st[i]); if ((base) == 0) atomicAdd(&stats[8], 1ull); } } while (0)
+                                for (int i = 0; i < 4; ++i) atomicAdd(&stats[(base) + i], st[((base) == 4 ? PSTAMP_PROD_FIRST : 0) + i]); if ((base) == 0) atomicAdd(&stats[8], 1ull); } } while (0)
 #else
 #define PSTAMP(i) do {} while (0)
 #define PSTAMP_INIT do {} while (0)
@@ -145,6 +163,7 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
     float* s_x0 = smem + 2 * TILE * LDA;              // [2][TILE * LDA]  raw self rows (residual); then the output tile
     int* s_tile = reinterpret_cast<int*>(smem + 4 * TILE * LDA);                  // [8] ring of tile ids
     int* s_sync = s_tile + 8;                         // consumer-only tile counter (CLS)
+    int* s_prod = s_tile + 9;                         // [2] producer-only counters (FSPLIT, FOLD = 1: the two meetings around their product)
     int* s_cd = s_tile + 16;                          // [2][8 segments][4] descriptor words of the consumers' epilogue (below)
     float* s_dis0 = smem + PS_LDS_DIS;                // [2][TILE] (deg+1)^-1/2 of the tile's rows (child sums of the output)
     float* s_pat = smem + PS_LDS_PAT;                 // [n_pats][64] weight patterns, quad layout (seg_wide.h)
@@ -184,6 +203,7 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
             s_bn[3 * C + tid] = ca.t1[tid];
         }
         if (tid == 0) *s_sync = 0;
+        if (FSPLIT && FOLD == 1 && tid == 0) { s_prod[0] = 0; s_prod[1] = 0; }
     }
     __syncthreads();
 
@@ -210,7 +230,7 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
         if constexpr (FSPLIT) {
             fs_load_w(W, wave, lane_k, fw[0], FOLD == 2 ? flo : nullptr);
             if (FOLD == 1) {
-                fs_load_w(ca.w1, wave, lane_k, fw[1], nullptr);
+                if (EG_FOLD_PROD_RB < 4) fs_load_w(ca.w1, wave, lane_k, fw[1], nullptr);      // (4: every residual unit is the producers')
                 ring_load(0); ring_load(1);
             }
         }
@@ -615,60 +635,92 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
                     // NEXT tile's phase 1 behind the chain's last guard: both in front of the tile's logit stores, so the wait at
                     // the top of the next tile is for loads older than the stores (see s_cd above).  The accumulation order is
                     // the unit order, the same for every tile.
-                    constexpr int NU = FOLD == 1 ? 32 : 16;
                     const int j16f = lane & 15, kqf = lane >> 4;
                     const float* pa = s_a + j16f * LDA + koff16(kqf);
                     const float* px = s_x + j16f * LDA + koff16(kqf);
-                    auto frag = [&](int u, f32x4 (&r)[2]) {
-                        const f32x4* b = reinterpret_cast<const f32x4*>((u < 16 ? pa : px) + 16 * (u & 3) * LDA + 8 * ((u >> 2) & 3));
-                        r[0] = b[0]; r[1] = b[1];
-                    };
                     f32x4v fa[4][2];
+                    if constexpr (FOLD == 2) {                   // (M alone, its lo plane resident; this body's device code is kept as it
+                        constexpr int NU = 16;                   // was: the loop below is the one tile.h fs_chain was made from)
+                        auto frag = [&](int u, f32x4 (&r)[2]) {
+                            const f32x4* b = reinterpret_cast<const f32x4*>(pa + 16 * (u & 3) * LDA + 8 * ((u >> 2) & 3));
+                            r[0] = b[0]; r[1] = b[1];
+                        };
 #pragma unroll
-                    for (int cb = 0; cb < 2; ++cb) {
-                        const f32x4 q = *reinterpret_cast<const f32x4*>(s_bn + 32 * wave + 16 * cb + 4 * kqf);
+                        for (int cb = 0; cb < 2; ++cb) {
+                            const f32x4 q = *reinterpret_cast<const f32x4*>(s_bn + 32 * wave + 16 * cb + 4 * kqf);
 #pragma unroll
-                        for (int rb = 0; rb < 4; ++rb) fa[rb][cb] = f32x4v{q.x, q.y, q.z, q.w};
-                    }
-                    f32x4 raw[2][2];
-                    Pieces set[2];
-                    frag(0, raw[0]); frag(1, raw[1]);
-                    set[0] = fs_split3_x8(raw[0][0], raw[0][1]);
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int u = 0; u < NU; ++u) {
-                        const int p = u >> 2, rb = u & 3, m = p >> 2, s = p & 3;
-                        const Pieces& cur = set[u & 1];
-                        const bf16x8 (&wlo)[2] = FOLD == 1 ? ring[p & 1] : flo[s];
-                        keep_pieces(cur);
-                        fs_step<0>(fw[m].hi[s], fw[m].mid[s], wlo, cur, fa[rb]);
-                        if (u >= 1) {
-                            fs_operand_guard(fa[(u - 1) & 3][0], fa[(u - 1) & 3][1]);
-                            keep_pieces(set[(u + 1) & 1]);
-                            if (FOLD == 1 && rb == 0) {
-                                keep_lo(ring[(p + 1) & 1]);
-                                __builtin_amdgcn_sched_barrier(0);
-                                ring_load((p + 1) & 7);
-                            }
-                            if (u == 15) a_tile_done();         // (the last fragments of s_a went into set[1] a unit ago)
+                            for (int rb = 0; rb < 4; ++rb) fa[rb][cb] = f32x4v{q.x, q.y, q.z, q.w};
                         }
+                        f32x4 raw[2][2];
+                        Pieces set[2];
+                        frag(0, raw[0]); frag(1, raw[1]);
+                        set[0] = fs_split3_x8(raw[0][0], raw[0][1]);
                         __builtin_amdgcn_sched_barrier(0);
-                        if (u + 1 < NU) set[(u + 1) & 1] = fs_split3_x8(raw[(u + 1) & 1][0], raw[(u + 1) & 1][1]);
-                        if (u + 2 < NU) frag(u + 2, raw[u & 1]);
-                        fs_step<1>(fw[m].hi[s], fw[m].mid[s], wlo, cur, fa[rb]);
-                        if (u + 1 < NU) {
 #pragma unroll
-                            for (int q = 0; q < 10; ++q) {          // one MFMA, then four of the split's vector instructions (groups of
-                                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // 2, 5 and 10 MFMAs measured 1 - 4 % slower per tile)
-                                __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+                        for (int u = 0; u < NU; ++u) {
+                            const int s = u >> 2, rb = u & 3;
+                            const Pieces& cur = set[u & 1];
+                            const bf16x8 (&wlo)[2] = flo[s];
+                            keep_pieces(cur);
+                            fs_step<0>(fw[0].hi[s], fw[0].mid[s], wlo, cur, fa[rb]);
+                            if (u >= 1) {
+                                fs_operand_guard(fa[(u - 1) & 3][0], fa[(u - 1) & 3][1]);
+                                keep_pieces(set[(u + 1) & 1]);
+                                if (u == 15) a_tile_done();         // (the last fragments of s_a went into set[1] a unit ago)
+                            }
+                            __builtin_amdgcn_sched_barrier(0);
+                            if (u + 1 < NU) set[(u + 1) & 1] = fs_split3_x8(raw[(u + 1) & 1][0], raw[(u + 1) & 1][1]);
+                            if (u + 2 < NU) frag(u + 2, raw[u & 1]);
+                            fs_step<1>(fw[0].hi[s], fw[0].mid[s], wlo, cur, fa[rb]);
+                            if (u + 1 < NU) {
+#pragma unroll
+                                for (int q = 0; q < 10; ++q) {          // one MFMA, then four of the split's vector instructions (groups of
+                                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // 2, 5 and 10 MFMAs measured 1 - 4 % slower per tile)
+                                    __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+                                }
+                            }
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                        fs_operand_guard(fa[3][0], fa[3][1]);
+                        keep_pieces(set[0]);
+                        keep_pieces(set[1]);
+                    } else {
+                        // FOLD = 1: the producers have left c + h W1s^T of row blocks < PRB in place over those rows of s_x (below, PRODUCER),
+                        // so these accumulators start from it and the residual units of those row blocks are not in this chain.
+                        constexpr int PRB = EG_FOLD_PROD_RB;                        // row blocks whose residual product the producers ran
+                        constexpr int NRES = 4 - PRB;                               // residual units per k-step left here
+                        constexpr int NU = 16 + 4 * NRES;
+                        constexpr int NPH = NRES ? 8 : 4;                           // phases this wave streams lo fragments for
+                        auto unit = [](int u) -> FsUnit {
+                            if (u < 16) return FsUnit{u >> 2, u & 3, 0, (u & 3) == 0};
+                            const int v = u - 16, nres = NRES ? NRES : 1;
+                            return FsUnit{4 + v / nres, PRB + v % nres, 1, v % nres == 0};
+                        };
+                        auto frag = [&](const FsUnit& c, f32x4 (&r)[2]) {
+                            const f32x4* b = reinterpret_cast<const f32x4*>((c.src ? px : pa) + 16 * c.rb * LDA + 8 * (c.p & 3));
+                            r[0] = b[0]; r[1] = b[1];
+                        };
+#pragma unroll
+                        for (int cb = 0; cb < 2; ++cb) {
+                            const f32x4 q = *reinterpret_cast<const f32x4*>(s_bn + 32 * wave + 16 * cb + 4 * kqf);
+#pragma unroll
+                            for (int rb = 0; rb < 4; ++rb) {
+                                const f32x4 q0 = rb < PRB ? *reinterpret_cast<const f32x4*>(s_x + (16 * rb + j16f) * LDA + 32 * wave + 16 * cb + 4 * kqf) : q;
+                                fa[rb][cb] = f32x4v{q0.x, q0.y, q0.z, q0.w};
                             }
                         }
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                    fs_operand_guard(fa[3][0], fa[3][1]);
-                    keep_pieces(set[0]);
-                    keep_pieces(set[1]);
-                    if (FOLD == 1) {
+                        fs_chain<NU>(unit, frag,
+                            [&](const FsUnit& c) -> const FsPlanes& { return fw[c.p >> 2]; },
+                            [&](const FsUnit& c) -> const bf16x8 (&)[2] { return ring[c.p & 1]; },
+                            fa,
+                            [&](int u, const FsUnit& c) {
+                                if (c.first) {
+                                    keep_lo(ring[(c.p + 1) & 1]);
+                                    __builtin_amdgcn_sched_barrier(0);
+                                    ring_load((c.p + 1) % NPH);
+                                }
+                                if (u == 15) a_tile_done();         // (the last fragments of s_a went into set[1] a unit ago)
+                            });
                         keep_lo(ring[1]);
                         __builtin_amdgcn_sched_barrier(0);
                         ring_load(1);
@@ -893,11 +945,14 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
                 // fully exposed memory round trip (the producers do most of their work after the consumers' MFMA chain has ended,
                 // DESIGN 5.22)
                 SegKidsum KS;
-                if (use_kin) segp_kidsum_issue(sd0, sd1, row_src(kin + (size_t)frame * a.kid_rows * C, a.kid_rows * (C * 4), lane), KS);
+                // (DIAG beside the producers' product, whose W1s planes stay in 64 registers: no room for these eight rows in the main
+                // stage, they are issued behind it -- the second round trip on aux tiles that the other forms avoid)
+                constexpr bool KS_LATE = DIAG && FSPLIT && FOLD == 1;
+                if (use_kin && !KS_LATE) segp_kidsum_issue(sd0, sd1, row_src(kin + (size_t)frame * a.kid_rows * C, a.kid_rows * (C * 4), lane), KS);
                 // unchained calls (a stack's first layer): the first segment's 16 child rows as well; the second segment's
                 // follow once the main stage has freed its registers
                 SegKids K0;
-                if (!RSEP && !DIAG && (sd0.aux & 1) && !use_kin) segw_kids_issue(sd0, pats, xs, lane, K0);      // (RSEP, DIAG: no registers left for them here)
+                if (!RSEP && !DIAG && !(FSPLIT && FOLD == 1) && (sd0.aux & 1) && !use_kin) segw_kids_issue(sd0, pats, xs, lane, K0);      // (RSEP, DIAG, the producers' product: no registers left for them here)
                 __builtin_amdgcn_sched_barrier(0);                  // every load of both segments is issued above this line
                 PSTAMP(PS_ISSUE);
                 const float* wqa = s_pat + sd0.pat * PATQ + 32 * (lane >> 5);      // this lane's weights (LDS, quad layout)
@@ -934,9 +989,10 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
                 __builtin_amdgcn_sched_barrier(0);
                 PSTAMP(PS_MAIN);
                 if (use_kin) {
+                    if (KS_LATE) segp_kidsum_issue(sd0, sd1, row_src(kin + (size_t)frame * a.kid_rows * C, a.kid_rows * (C * 4), lane), KS);
                     segp_kidsum_add(KS, wqa, wqb, acc0, acc1);
                 } else if (sd0.aux & 1) {                           // uniform: aux level, children pulled as rows
-                    if (RSEP || DIAG) segw_kids_issue(sd0, pats, xs, lane, K0);
+                    if (RSEP || DIAG || (FSPLIT && FOLD == 1)) segw_kids_issue(sd0, pats, xs, lane, K0);
                     segw_kids_add(lane, K0, acc0);
                     pin_acc4(acc0);                                 // (issuing the second segment's loads ahead of this add measured slower)
                     {
@@ -981,6 +1037,79 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
             }
             PSTAMP(2);
         };
+        // FSPLIT, FOLD = 1: behind the rows of a tile this wave runs the residual product of row blocks 0 .. PRB - 1
+        // for the column slice of consumer wave p -- c + h W1s^T, the units of the consumers' chain (tile.h fs_chain), step-major
+        // over s_x[buf] -- and leaves the sums in place over those rows and its 32 columns of s_x[buf], where consumer wave p takes
+        // them as its accumulators' initial values.  The hi and mid planes of the W1s slice are split once; the lo fragments come
+        // from the table's entries [1][s][p][cb][lane], eight loads per tile in front of the first meeting (resident, 32 VGPRs more
+        // across produce(), the role spilled).
+        // Every producer reads all 128 columns of those rows and writes 32 of them, so two producer-only meetings bracket the
+        // product (LDS counters, the consumers' a_tile_done / a_tile_free): before its first fragment read all four waves have
+        // written their rows of s_x[buf]; before its first write all four have their last fragment in registers.  Both run once
+        // per produced tile in every producer wave -- product() runs for exactly the tiles produce() ran for, under the same
+        // workgroup-uniform condition (the tile's id is not negative; see the loop below) -- so the count a wave waits for is
+        // 4 x the tiles produced so far.
+        constexpr bool PROD = FSPLIT && FOLD == 1;
+        constexpr int PRB = EG_FOLD_PROD_RB;
+        FsPlanes pw;
+        bf16x8 plo[4][2];
+        int n_made = 0;
+        if constexpr (PROD) fs_load_w(ca.w1, p, lane_k, pw, nullptr);
+        auto product = [&](int buf, int lane) {
+            asm volatile("" : "+v"(lane));
+            const __amdgpu_buffer_rsrc_t lo_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(scale), 0, 65536, 0x00020000);
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+#pragma unroll
+                for (int cb = 0; cb < 2; ++cb)
+                    plo[s][cb] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(lo_rsrc, (128 * p + lane) * 16, 8192 * (4 + s) + 1024 * cb, 0));
+            float* s_x = s_x0 + buf * TILE * LDA;
+            const int target = 4 * ++n_made;
+            auto arrive = [&](int* ctr) {
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                if (lane == 0) __hip_atomic_fetch_add(ctr, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+            };
+            auto await = [&](int* ctr) {
+                while (__hip_atomic_load(ctr, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < target) __builtin_amdgcn_s_sleep(1);
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            };
+            arrive(&s_prod[0]);                            // this wave's rows of s_x[buf] are written ...
+            await(&s_prod[0]);                             // ... and so are the other three's
+            PSTAMP(4);
+            if (EG_FOLD_PROD_PRIO != 3) __builtin_amdgcn_s_setprio(EG_FOLD_PROD_PRIO);
+            const int j16 = lane & 15, kq = lane >> 4;
+            const float* px = s_x + j16 * LDA + koff16(kq);
+            f32x4v fa[PRB][2];
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) {
+                const f32x4 q = *reinterpret_cast<const f32x4*>(s_bn + 32 * p + 16 * cb + 4 * kq);
+#pragma unroll
+                for (int rb = 0; rb < PRB; ++rb) fa[rb][cb] = f32x4v{q.x, q.y, q.z, q.w};
+            }
+            fs_chain<4 * PRB>([](int u) -> FsUnit { return FsUnit{4 + u / PRB, u % PRB, 1, u % PRB == 0}; },
+                [&](const FsUnit& c, f32x4 (&r)[2]) {
+                    const f32x4* b = reinterpret_cast<const f32x4*>(px + 16 * c.rb * LDA + 8 * (c.p & 3));
+                    r[0] = b[0]; r[1] = b[1];
+                },
+                [&](const FsUnit&) -> const FsPlanes& { return pw; },
+                [&](const FsUnit& c) -> const bf16x8 (&)[2] { return plo[c.p & 3]; },
+                fa,
+                [&](int u, const FsUnit&) {
+                    if (u == 4 * PRB - 1) arrive(&s_prod[1]);      // (the last fragments went into a piece set a unit ago)
+                });
+            PSTAMP(5);
+            await(&s_prod[1]);                             // nobody reads these rows of s_x[buf] any more
+            PSTAMP(6);
+#pragma unroll
+            for (int rb = 0; rb < PRB; ++rb)
+#pragma unroll
+                for (int cb = 0; cb < 2; ++cb) {
+                    const f32x4v z = fa[rb][cb];
+                    *reinterpret_cast<f32x4*>(s_x + (16 * rb + j16) * LDA + 32 * p + 16 * cb + 4 * kq) = f32x4{z.x, z.y, z.z, z.w};
+                }
+            if (EG_FOLD_PROD_PRIO != 3) __builtin_amdgcn_s_setprio(3);
+            PSTAMP(7);
+        };
         int dv_next = 0;
         {
             const int t0 = __builtin_amdgcn_readfirstlane(s_tile[0]);
@@ -988,9 +1117,17 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
             if (t0 >= 0) produce(t0, 0, lane_k, load_desc(t0, lane_k));
             if (t1 >= 0) dv_next = load_desc(t1, lane_k);
         }
-        __syncthreads();                                   // tile 0 is in buffer 0
+        // PROD: the tile barrier stands at the top of the iteration instead of its end -- the prologue's is barrier 0 -- so that the
+        // product of tile k, prologue's tile 0 included, has ONE place in the code: in front of barrier k, behind the produce() of
+        // iteration k - 1.  Tile k was produced if and only if its id is not negative (the id was written three barriers ago).
+        if constexpr (!PROD) __syncthreads();              // tile 0 is in buffer 0
         for (int k = 0;; ++k) {
             const int t_cur = __builtin_amdgcn_readfirstlane(s_tile[k & 7]);
+            if constexpr (PROD) {
+                if (t_cur >= 0) product(k & 1, lane_k);
+                __syncthreads();                           // barrier k
+                PSTAMP(3);
+            }
             if (t_cur < 0) break;
             const int t_next = __builtin_amdgcn_readfirstlane(s_tile[(k + 1) & 7]);
             const int t_nn = __builtin_amdgcn_readfirstlane(s_tile[(k + 2) & 7]);
@@ -1007,8 +1144,10 @@ __global__ __launch_bounds__(PS_THREADS, 2) void k_gcn_layer_ps(const float* __r
                 if (walk_static) s_tile[(k + 3) & 7] = ps_static_tile(k + 3, n_tiles);
                 else ps_claim_commit(counters, group, n_tiles, got, &s_tile[(k + 3) & 7]);
             }
-            __syncthreads();                               // barrier k+1
-            PSTAMP(3);
+            if constexpr (!PROD) {
+                __syncthreads();                           // barrier k+1
+                PSTAMP(3);
+            }
         }
         if (TRAIN) {                                       // the consumers' hand-over of the statistics (two barriers)
             __syncthreads();

@@ -840,6 +840,56 @@ __device__ inline void fs_step(const bf16x8 (&whi)[2], const bf16x8 (&wmid)[2], 
 #undef FS_MFMA
 }
 
+// The chain of units both roles of the folded body run (gcn_layer_ps.hip).  A unit is 12 MFMAs of one 16-row block
+// on one (matrix, step) phase: p = 4 m + s, tile src (0: the aggregated rows, 1: the raw rows), first = the unit opens its phase.
+// unit(u) names unit u -- the accumulation order is the unit order --, frag(unit, r) reads its two 16-byte fragments, planes(unit)
+// and lo(unit) give the weight pieces of its phase.  Unit u runs on piece set u & 1; behind its first two MFMAs the guard of unit
+// u - 1 frees the other set, behind_guard(u, unit) runs there (whatever writes a register unit u - 1 read: the operand rule of
+// DESIGN_NOTES 5.14), the split of unit u + 1 is written into that set beside the other ten MFMAs and the fragments of unit u + 2
+// are read.  fa[rb]: the two accumulators of row block rb.
+struct FsUnit { int p, rb, src; bool first; };
+
+template <int NU, int NRB, typename U, typename F, typename W, typename L, typename G>
+__device__ inline void fs_chain(U unit, F frag, W planes, L lo, f32x4v (&fa)[NRB][2], G behind_guard) {
+    f32x4 raw[2][2];
+    Pieces set[2];
+    frag(unit(0), raw[0]); frag(unit(1), raw[1]);
+    set[0] = fs_split3_x8(raw[0][0], raw[0][1]);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+        const FsUnit c = unit(u);
+        const int s = c.p & 3;
+        const FsPlanes& w = planes(c);
+        const bf16x8 (&wlo)[2] = lo(c);
+        const Pieces& cur = set[u & 1];
+        keep_pieces(cur);
+        fs_step<0>(w.hi[s], w.mid[s], wlo, cur, fa[c.rb]);
+        if (u >= 1) {
+            const int rb_prev = unit(u - 1).rb;
+            fs_operand_guard(fa[rb_prev][0], fa[rb_prev][1]);
+            keep_pieces(set[(u + 1) & 1]);
+            behind_guard(u, c);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (u + 1 < NU) set[(u + 1) & 1] = fs_split3_x8(raw[(u + 1) & 1][0], raw[(u + 1) & 1][1]);
+        if (u + 2 < NU) frag(unit(u + 2), raw[u & 1]);
+        fs_step<1>(w.hi[s], w.mid[s], wlo, cur, fa[c.rb]);
+        if (u + 1 < NU) {
+#pragma unroll
+            for (int q = 0; q < 10; ++q) {          // one MFMA, then four of the split's vector instructions (groups of
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // 2, 5 and 10 MFMAs measured 1 - 4 % slower per tile)
+                __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    const int rb_last = unit(NU - 1).rb;
+    fs_operand_guard(fa[rb_last][0], fa[rb_last][1]);
+    keep_pieces(set[0]);
+    keep_pieces(set[1]);
+}
+
 // ---- persistent tile walk ------------------------------------------------------------------
 // Tiles that are neighbours in the node order share halo rows (grid rows +-1, parents), so they
 // should be processed on the SAME XCD (same L2) at about the same time.  Three modes:
