@@ -1,6 +1,7 @@
 """The optimizer update of the training step as ONE launch per step: ``Adam`` (``eg_adam_step``, csrc/adam.hip), ``SGD`` and ``RMSprop``
 (``eg_sgd_step`` / ``eg_rmsprop_step``, csrc/optim.hip) -- the three names of the reference's optimizer registry
-(src/builders/optimizer_builder.py), with its builder (``OPTIMIZERS``, ``build``).
+(src/builders/optimizer_builder.py), with its builder (``OPTIMIZERS``, ``build``).  All three are one kernel and one host function
+(csrc/multi_tensor.h) around a dozen lines of arithmetic each.
 
 The reference trains with ``torch.optim.Adam`` (src/engine.py's optimizer builder).  torch's fused form is a ``_foreach_add_`` on
 the step counts plus one multi-tensor launch per ~30 tensors: 4 launches (34 us of a 0.9-ms captured batch-1 step) for the 73
@@ -28,40 +29,33 @@ import torch
 
 from . import _lib
 
-_MAX_TENSORS = 96                                       # eg_adam_step's per-launch maximum
+_MAX_TENSORS = 96                                       # EG_ADAM_MAX_TENSORS
 _SGD_MAX_TENSORS = 120                                  # EG_SGD_MAX_TENSORS
 _RMSPROP_MAX_TENSORS = 84                               # EG_RMSPROP_MAX_TENSORS
 
 
-class _AdamTensor(ct.Structure):
-    """eg_adam_tensor (include/echoglad_hip.h)"""
-    _fields_ = [("param", ct.c_void_p), ("grad", ct.c_void_p), ("exp_avg", ct.c_void_p), ("exp_avg_sq", ct.c_void_p), ("numel", ct.c_int64)]
+def _entry_type(name, *state):
+    """The table entry of one update (eg_adam_tensor, eg_sgd_tensor, eg_rmsprop_tensor of include/echoglad_hip.h): param, grad, the
+    state arrays under torch's state keys, numel."""
+    fields = [(f, ct.c_void_p) for f in ("param", "grad") + state] + [("numel", ct.c_int64)]
+    return type(name, (ct.Structure,), {"_fields_": fields})
 
 
-class _SGDTensor(ct.Structure):
-    """eg_sgd_tensor (include/echoglad_hip.h)"""
-    _fields_ = [("param", ct.c_void_p), ("grad", ct.c_void_p), ("momentum_buffer", ct.c_void_p), ("numel", ct.c_int64)]
-
-
-class _RMSpropTensor(ct.Structure):
-    """eg_rmsprop_tensor (include/echoglad_hip.h)"""
-    _fields_ = [("param", ct.c_void_p), ("grad", ct.c_void_p), ("square_avg", ct.c_void_p), ("grad_avg", ct.c_void_p),
-                ("momentum_buffer", ct.c_void_p), ("numel", ct.c_int64)]
+_AdamTensor = _entry_type("_AdamTensor", "exp_avg", "exp_avg_sq")
+_SGDTensor = _entry_type("_SGDTensor", "momentum_buffer")
+_RMSpropTensor = _entry_type("_RMSpropTensor", "square_avg", "grad_avg", "momentum_buffer")
 
 
 class _OneLaunch(torch.optim.Optimizer):
     """What the three optimizers share: the step loop, the prepared-launch cache and the per-launch count arrays.  A subclass names
-    its table entry (``_ENTRY``), its per-launch maximum (``_MAX``), the state tensors a group's update uses (``_names``), how an entry
-    is filled (``_entry``) and the call itself (``_launch``)."""
+    its table entry (``_ENTRY``: a state array that a group's update does not use is NULL there), its per-launch maximum (``_MAX``),
+    the state tensors a group's update uses (``_names``) and the call itself (``_launch``)."""
     _ENTRY = None
     _MAX = 0
     _ALWAYS_CAPTURABLE = True                           # load_state_dict keeps ``capturable`` set, whatever the saved groups say
 
     def _names(self, group):
         """The keys of the state tensors (beside ``step``) that this group's update reads and writes, in the table's order."""
-        raise NotImplementedError
-
-    def _entry(self, group, p, tensors):
         raise NotImplementedError
 
     def _launch(self, lib, group, table, count, counts, lr, lr_dev, stream):
@@ -161,6 +155,7 @@ class _OneLaunch(torch.optim.Optimizer):
                       or not t.is_contiguous()):
                     raise RuntimeError(f"{self._who}: state[p]['{name}'] must be a contiguous float32 tensor of the parameter's size on its device")
         out = []
+        fields = [f for f, _ in self._ENTRY._fields_[2:-1]]
         for lo in range(0, len(ps), self._MAX):
             part = ps[lo:lo + self._MAX]
             counts, views = self._counts_of(part)
@@ -169,7 +164,7 @@ class _OneLaunch(torch.optim.Optimizer):
             for k, p in enumerate(part):
                 st = self.state[p]
                 tensors = tuple(st[name] for name in names)
-                table[k] = self._entry(group, p, tensors)
+                table[k] = self._ENTRY(p.data_ptr(), p.grad.data_ptr(), *[st[f].data_ptr() if f in names else None for f in fields], p.numel())
                 moments.append(tensors)
             out.append((part, table, counts, views, moments))
         return out
@@ -227,9 +222,6 @@ class Adam(_OneLaunch):
     def _names(self, group):
         return ("exp_avg", "exp_avg_sq")
 
-    def _entry(self, group, p, tensors):
-        return _AdamTensor(p.data_ptr(), p.grad.data_ptr(), tensors[0].data_ptr(), tensors[1].data_ptr(), p.numel())
-
     def _launch(self, lib, group, table, count, counts, lr, lr_dev, stream):
         b1, b2 = group["betas"]
         _lib.check(lib.eg_adam_step(table, count, counts, lr, lr_dev, float(b1), float(b2), float(group["eps"]),
@@ -271,9 +263,6 @@ class SGD(_OneLaunch):
                     self.state[p]["step"] = 0.0
         return super()._prepare(ps, on_device, group, names)
 
-    def _entry(self, group, p, tensors):
-        return _SGDTensor(p.data_ptr(), p.grad.data_ptr(), tensors[0].data_ptr() if tensors else None, p.numel())
-
     def _launch(self, lib, group, table, count, counts, lr, lr_dev, stream):
         _lib.check(lib.eg_sgd_step(table, count, counts, lr, lr_dev, float(group["momentum"]), float(group["dampening"]),
                                    float(group["weight_decay"]), int(bool(group["nesterov"])), int(bool(group["maximize"])), stream),
@@ -304,11 +293,6 @@ class RMSprop(_OneLaunch):
 
     def _names(self, group):
         return ("square_avg",) + (("grad_avg",) if group["centered"] else ()) + (("momentum_buffer",) if group["momentum"] > 0 else ())
-
-    def _entry(self, group, p, tensors):
-        by = dict(zip(self._names(group), tensors))
-        ptr = lambda name: by[name].data_ptr() if name in by else None          # noqa: E731
-        return _RMSpropTensor(p.data_ptr(), p.grad.data_ptr(), ptr("square_avg"), ptr("grad_avg"), ptr("momentum_buffer"), p.numel())
 
     def _launch(self, lib, group, table, count, counts, lr, lr_dev, stream):
         _lib.check(lib.eg_rmsprop_step(table, count, counts, lr, lr_dev, float(group["alpha"]), float(group["eps"]),

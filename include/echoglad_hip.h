@@ -549,7 +549,7 @@ int eg_coord_update_bwd(float* dx, int64_t n_per_frame, int64_t coord_base, int6
  * tensors: HOST array of `count` entries (device pointers; they travel in the kernel arguments, so a captured launch keeps them);
  * steps: [count] device floats, the number of updates of each tensor so far.  lr_device (nullable): the learning rate as a device float,
  * read by the kernel instead of `lr` -- what a scheduler changes between the replays of a captured step.  EG_ERR_UNSUPPORTED (nothing
- * launched) for count > 96. */
+ * launched) for count > EG_ADAM_MAX_TENSORS (96, below). */
 typedef struct eg_adam_tensor {
     float* param;
     const float* grad;
@@ -577,6 +577,7 @@ int eg_adam_step(const eg_adam_tensor* tensors, int count, float* steps, float l
  *   momentum > 0:  buf = momentum * buf + g / avg;  p -= lr * buf                     else:  p -= lr * g / avg;   then steps[k] += 1
  * grad_avg non-NULL exactly when centered, momentum_buffer non-NULL exactly when momentum > 0, else EG_ERR_ARG; EG_ERR_ARG as well
  * for alpha, eps, momentum or weight_decay < 0. */
+#define EG_ADAM_MAX_TENSORS 96
 #define EG_SGD_MAX_TENSORS 120
 #define EG_RMSPROP_MAX_TENSORS 84
 typedef struct eg_sgd_tensor {

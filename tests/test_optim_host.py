@@ -1,5 +1,5 @@
 """CPU: the host side of the one-launch SGD and RMSprop (csrc/optim.hip, echoglad_amd/optim.py) -- the refusals of eg_sgd_step /
-eg_rmsprop_step that come before any HIP call, the registry and builder, the state-dict round trip with torch's classes and the
+eg_rmsprop_step (and eg_adam_step, csrc/adam.hip: one host function, csrc/multi_tensor.h) that come before any HIP call, the registry and builder, the state-dict round trip with torch's classes and the
 prepared-launch cache walked on CPU tensors.  Nothing is launched."""
 import copy
 import ctypes as ct
@@ -11,7 +11,7 @@ import torch
 from echoglad_amd import _lib, optim
 from echoglad_amd.optim import SGD, Adam, RMSprop, _prepared_valid
 
-SGD_MAX, RMSPROP_MAX = 120, 84
+SGD_MAX, RMSPROP_MAX, ADAM_MAX = 120, 84, 96
 
 
 # ---- ABI ------------------------------------------------------------------------------------------------------------------------------
@@ -23,12 +23,13 @@ def test_header_and_binding_declare_abi_155():
     assert "155: eg_sgd_step, eg_rmsprop_step" in open(_lib.__file__).read()
     assert f"#define EG_SGD_MAX_TENSORS {SGD_MAX}" in text and f"#define EG_RMSPROP_MAX_TENSORS {RMSPROP_MAX}" in text
     assert (optim._SGD_MAX_TENSORS, optim._RMSPROP_MAX_TENSORS, optim._MAX_TENSORS) == (SGD_MAX, RMSPROP_MAX, 96)
+    assert f"#define EG_ADAM_MAX_TENSORS {ADAM_MAX}" in text and optim._MAX_TENSORS == ADAM_MAX
     f, p, i = ct.c_float, ct.c_void_p, ct.c_int
     assert _lib.SIGNATURES["eg_sgd_step"] == (i, [p, i, p, f, p, f, f, f, i, i, p])
     assert _lib.SIGNATURES["eg_rmsprop_step"] == (i, [p, i, p, f, p, f, f, f, f, i, i, p])
     assert {"eg_sgd_step", "eg_rmsprop_step"} <= _lib.TAKES_STREAM
     # the ctypes entries follow the header's field order
-    for cls, name in ((optim._SGDTensor, "eg_sgd_tensor"), (optim._RMSpropTensor, "eg_rmsprop_tensor")):
+    for cls, name in ((optim._SGDTensor, "eg_sgd_tensor"), (optim._RMSpropTensor, "eg_rmsprop_tensor"), (optim._AdamTensor, "eg_adam_tensor")):
         body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), re.sub(r"/\*.*?\*/", "", text, flags=re.S), flags=re.S).group(1)
         assert [n for n, _ in cls._fields_] == re.findall(r"(\w+);", body)
         assert ct.sizeof(cls) == 8 * len(cls._fields_)
@@ -93,6 +94,32 @@ def test_rmsprop_step_refusals(built_lib):
     assert _rms(lib, _rms_table(RMSPROP_MAX + 1), RMSPROP_MAX + 1) == UNS and "split" in _lib.last_error()
     assert _rms(lib, _rms_table(RMSPROP_MAX + 1, ga=FAKE, buf=FAKE), RMSPROP_MAX + 1, centered=1, momentum=0.9) == UNS
     assert _rms(lib, t, 0) == _lib.EG_OK
+
+
+def _adam_table(count, m=FAKE, v=FAKE, numel=8):
+    return (optim._AdamTensor * max(count, 1))(*[optim._AdamTensor(FAKE, FAKE, m, v, numel) for _ in range(count)])
+
+
+def _adam(lib, table, count, steps=FAKE, beta1=0.9, beta2=0.999, eps=1e-8):
+    return lib.eg_adam_step(table, count, steps, 1e-3, None, beta1, beta2, eps, 0.0, 0, None)
+
+
+def test_adam_step_refusals(built_lib):
+    lib = _lib.load()
+    ARG, UNS = _lib.EG_ERR_ARG, _lib.EG_ERR_UNSUPPORTED
+    t = _adam_table(2)
+    assert _adam(lib, None, 2) == ARG and _adam(lib, t, 2, steps=None) == ARG and _adam(lib, t, -1) == ARG
+    for kw in (dict(beta1=-0.1), dict(beta1=1.0), dict(beta2=-0.1), dict(beta2=1.0), dict(beta1=float("nan")), dict(beta2=float("nan")),
+               dict(eps=-1e-8)):
+        assert _adam(lib, t, 2, **kw) == ARG and "betas" in _lib.last_error(), kw
+    assert _adam(lib, _adam_table(2, m=None), 2) == ARG and _adam(lib, _adam_table(2, v=None), 2) == ARG
+    assert _adam(lib, _adam_table(2, numel=0), 2) == ARG and _adam(lib, _adam_table(2, numel=1 << 31), 2) == ARG
+    bad = _adam_table(2)
+    bad[1].grad = None
+    assert _adam(lib, bad, 2) == ARG
+    assert _adam(lib, _adam_table(ADAM_MAX + 1), ADAM_MAX + 1) == UNS and "split" in _lib.last_error()
+    assert _adam(lib, _adam_table(ADAM_MAX + 1), ADAM_MAX + 1, beta1=1.5) == ARG                      # (a bad hyper-parameter first)
+    assert _adam(lib, t, 0) == _lib.EG_OK                                                             # nothing to do, nothing launched
 
 
 def test_constructor_checks_are_torchs():
