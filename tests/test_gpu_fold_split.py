@@ -6,8 +6,8 @@ launch-to-launch and batch determinism, once at full grid.
 
 Which lo fragment goes with which (matrix, k-step, column block) is NOT pinned by the float64 cases over whole arrays: a lo plane
 is worth 2^-16 of a product, and the rule's yardstick, the worst fp32 error of the array, leaves room for that (mutation builds,
-profiles/fold_split_ab.txt 8; nor does it see a left-out mid.mid product, node by node either: the model's oracle test in
-tests/test_gpu_fold_heads.py is what catches that).  Each half is therefore checked alone with a hand-made table over zero hi and mid planes: W1s exactly, with inputs that are powers of two, M -- which
+profiles/fold_split_ab.txt 8; nor does it see a left-out mid.mid product, node by node either: tests/test_gpu_fold_probe.py is
+what catches that, product by product through probe heads, profiles/fold_probe_mutations.txt).  Each half is therefore checked alone with a hand-made table over zero hi and mid planes: W1s exactly, with inputs that are powers of two, M -- which
 multiplies aggregated rows, which are not -- within the bound that hi()'s 8 significant bits give."""
 import contextlib
 import os
