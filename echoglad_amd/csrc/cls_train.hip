@@ -13,7 +13,9 @@
 //             k_cls_mid_fwd         h1 = drop(relu(bn1(z1)));  z2 = h1 W2^T + b2 per head, column sums of z2, z2^2
 //             k_cls_out_fwd         h2 = drop(relu(bn2(z2)));  logit = h2 . w3 + b3
 //   backward  k_cls_out_bwd_sums    g2 = dlogit w3 mask2:  sum g2, sum g2 xhat2 (-> dgamma2, dbeta2), dw3, db3
-//             k_cls_mid_bwd         dz2 = bn2'(g2);  dW2 += dz2^T h1;  dh1 = dz2 W2   (pre-mask gradient of h1)
+//             k_cls_mid_bwd         dz2 = bn2'(g2);  dW2 += dz2^T h1;  dh1 = dz2 W2;  sum g1, sum g1 xhat1 (g1 = dh1 mask1)
+//             k_cls_first_bwd       dz1 = bn1'(g1) on load;  dW1 += dz1^T h[valid rows];  dh[valid rows] = dz1 W1
+//          where k_cls_first_bwd does not cover the shape (no dh wanted, fewer than 64 valid rows per frame, 2^32 elements):
 //             eg_bn_act_bwd         dz1 = bn1'(dh1 mask1), dgamma1, dbeta1                                  (train.hip)
 //             k_lin128_map          dh[valid rows] = dz1 W1                                          (transposed W)
 //             k_dweight_partial     dW1 = dz1^T h[valid rows]                                               (train.hip)
@@ -55,25 +57,10 @@ struct LinMapDims {
     int in_stride, in_lo, out_stride, out_lo;
 };
 
-// ACT: the input rows do not exist yet -- x = relu|id(dropout(z * scale + shift)) + residual is the activation pass of the
-// GNN layer in front of the heads (eg_gcn_layer_train_fwd with out == NULL left z and the statistics).  The tiles then cover
-// EVERY row of a frame (the heads' filter only masks the product's output rows), each row of x is written to `h` on the way
-// into LDS, and the separate activation pass + its 512 B per row of re-read are gone.
-struct LinAct {
-    const float *z, *scale, *shift, *residual;
-    float* h;
-    ActArgs a;
-    int h_skip_lo, h_skip_hi;       // rows [h_skip_lo, h_skip_hi) of every frame are NOT written to h (0, 0: all rows are): the heads' backward
-                                    // recomputes them from z and the residual (eg_classifier_bwd_sums recompute_h), so only the rows the
-                                    // heads' filter drops -- the coordinate rows the landmark MLP reads -- ever reach memory
-};
-
-template <bool STATS, bool ACT>
+template <bool STATS>
 __global__ __launch_bounds__(512, 4) void k_lin128_map(const float* __restrict__ x, const float* __restrict__ W,
                                                        const float* __restrict__ bias, float* __restrict__ out,
-                                                       float* __restrict__ partial, const LinMapDims a, const LinAct act_) {
-    LinAct act = act_;
-    act.a = resolved(act_.a);
+                                                       float* __restrict__ partial, const LinMapDims a) {
     __shared__ __attribute__((aligned(16))) float s_a[TILE * LDA + 4];
     const int tid = threadIdx.x, lane_k = tid & 63, wave = wave_id();
     float wreg[32];
@@ -87,38 +74,12 @@ __global__ __launch_bounds__(512, 4) void k_lin128_map(const float* __restrict__
         asm volatile("" : "+v"(lane));
         const int frame = tile / a.tiles_per_frame;
         const int n0 = (tile - frame * a.tiles_per_frame) * TILE;
-        const int span = ACT ? a.in_stride : a.n_valid;    // rows of a frame the tiles walk over
-        const int rows_here = (span - n0) < TILE ? (span - n0) : TILE;
-        // rows [lo, hi) of the tile have an output row (ACT: the heads' row filter; otherwise all of them)
-        const int lo = ACT ? (a.in_lo > n0 ? a.in_lo - n0 : 0) : 0;
-        const int hi = ACT ? ((a.in_lo + a.n_valid - n0) < rows_here ? (a.in_lo + a.n_valid - n0) : rows_here) : rows_here;
-        const size_t in_row0 = (size_t)frame * a.in_stride + (ACT ? 0 : a.in_lo) + n0;
-        float* __restrict__ of = out + ((size_t)frame * a.out_stride + a.out_lo) * C + ((long long)n0 - (ACT ? a.in_lo : 0)) * C;
+        const int rows_here = (a.n_valid - n0) < TILE ? (a.n_valid - n0) : TILE;
+        const size_t in_row0 = (size_t)frame * a.in_stride + a.in_lo + n0;
+        float* __restrict__ of = out + ((size_t)frame * a.out_stride + a.out_lo) * C + (long long)n0 * C;
         const int rl0 = 8 * wave;
         const PairLane pl{lane >> 5, lane & 31};
-        if (ACT) {
-            f32x4 zz[4], rr[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int r = rl0 + 2 * k + pl.h;
-                const size_t off = (in_row0 + (unsigned)(r < rows_here ? r : rows_here - 1)) * C + 4u * pl.q;
-                zz[k] = ldnt4(act.z + off);
-                rr[k] = act.residual ? ldnt4(act.residual + off) : f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-            const f32x4 sc = *reinterpret_cast<const f32x4*>(act.scale + 4 * pl.q);
-            const f32x4 sh = *reinterpret_cast<const f32x4*>(act.shift + 4 * pl.q);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int r = rl0 + 2 * k + pl.h;
-                const size_t off = (in_row0 + (unsigned)(r < rows_here ? r : rows_here - 1)) * C + 4u * pl.q;
-                f32x4 v = zz[k] * sc + sh;
-                if (act.a.p > 0.f) v *= keep_scale4(act.a.seed, (unsigned long long)off, act.a.p, act.a.inv_keep);
-                if (act.a.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-                v += rr[k];
-                *reinterpret_cast<f32x4*>(act.h + off) = v;             // (a missing row: the last row's value once more)
-                *reinterpret_cast<f32x4*>(&s_a[(rl0 + 2 * k + pl.h) * LDA + 4 * pl.q]) = v;
-            }
-        } else {
+        {
             const float* __restrict__ xf = x + in_row0 * C;
             f32x4 v[4];
 #pragma unroll
@@ -146,14 +107,7 @@ __global__ __launch_bounds__(512, 4) void k_lin128_map(const float* __restrict__
             }
         }
         __syncthreads();
-        if (ACT) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int r = rl0 + 2 * k + pl.h;
-                if (r >= lo && r < hi)
-                    *reinterpret_cast<f32x4*>(of + (long long)r * C + 4 * pl.q) = *reinterpret_cast<const f32x4*>(&s_a[r * LDA + 4 * pl.q]);
-            }
-        } else if (rl0 < rows_here) {                       // (uniform per wave) whole 512-B rows, a duplicate store for a missing row
+        if (rl0 < rows_here) {                              // (uniform per wave) whole 512-B rows, a duplicate store for a missing row
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int r = rl0 + 2 * k + pl.h;
@@ -165,7 +119,7 @@ __global__ __launch_bounds__(512, 4) void k_lin128_map(const float* __restrict__
             const int c = tid & 127, r0 = 16 * (tid >> 7);
 #pragma unroll 4
             for (int r = r0; r < r0 + 16; ++r) {
-                const float v = (r >= lo && r < hi) ? s_a[r * LDA + c] : 0.f;
+                const float v = r < rows_here ? s_a[r * LDA + c] : 0.f;
                 cs += v; cq += v * v;
             }
         }
@@ -180,11 +134,24 @@ __global__ __launch_bounds__(512, 4) void k_lin128_map(const float* __restrict__
     }
 }
 
-// The ACT + STATS form as a kernel of its own: 4 waves (each owns two 16-channel groups of the product, W slices in 64 VGPRs),
-// two workgroups per CU, and the 16 row loads per thread of the NEXT tile (z and the residual) issued right behind the first
-// barrier of the current one -- their round trip runs under this tile's products and write-back instead of in front of the next
-// tile's activation (k_lin128_map<true, true>, 8 waves without the prefetch: 1.07 ms at batch 32; this one: see DESIGN 3.3).
-// Same tiles per workgroup, same MFMA chain per output block, same per-thread sums as k_lin128_map: the results are the bits
+// Activation + first layers in one kernel: the input rows do not exist yet -- x = relu|id(dropout(z * scale + shift)) + residual
+// is the activation pass of the GNN layer in front of the heads (eg_gcn_layer_train_fwd with out == NULL left z and the
+// statistics).  The tiles cover EVERY row of a frame (the heads' filter only masks the product's output rows), each row of x is
+// written to `h` on the way into LDS, and the separate activation pass + its 512 B per row of re-read are gone.
+struct LinAct {
+    const float *z, *scale, *shift, *residual;
+    float* h;
+    ActArgs a;
+    int h_skip_lo, h_skip_hi;       // rows [h_skip_lo, h_skip_hi) of every frame are NOT written to h (0, 0: all rows are): the heads' backward
+                                    // recomputes them from z and the residual (eg_classifier_bwd_sums recompute_h), so only the rows the
+                                    // heads' filter drops -- the coordinate rows the landmark MLP reads -- ever reach memory
+};
+
+// 4 waves (each owns two 16-channel groups of the product, W slices in 64 VGPRs), two workgroups per CU, and the 16 row loads per
+// thread of the NEXT tile (z and the residual) issued right behind the first barrier of the current one -- their round trip runs
+// under this tile's products and write-back instead of in front of the next tile's activation (an 8-wave form without the
+// prefetch took 1.07 ms at batch 32; this one: see DESIGN 3.3).
+// Same tiles per workgroup, same MFMA chain per output block, same per-thread sums as k_lin128_map<true>: the results are the bits
 // eg_bn_act_fwd + eg_classifier_train_fwd give.
 __global__ __launch_bounds__(256, 2) void k_act_lin128(const float* __restrict__ W, const float* __restrict__ bias, float* __restrict__ out,
                                                        float* __restrict__ partial, const LinMapDims a, const LinAct act_) {
@@ -493,14 +460,30 @@ __global__ __launch_bounds__(CT_THREADS) void k_cls_out_bwd_sums(const float* __
     }
 }
 
+// ---- block partial of BatchNorm-backward sums ---------------------------------------------------------------------------------
+// Per-thread float4 pairs (sum, sum xhat) -> this block's slab of partials [blocks][2][128], for a block of 32 * GROUPS
+// threads of which thread t is in row group rg = t >> 5 and owns channels c4 = 4 (t & 31)..: the GROUPS threads that share a
+// channel group are added in the fixed order k = 0 .. GROUPS - 1.  red: GROUPS * 2 * 128 floats of LDS nobody reads any more
+// (the caller's barrier).  (s, sx by value: by reference they are stack objects of the caller until the helper is inlined, and
+// k_cls_mid_bwd's schedule moves.)
+template <int GROUPS>
+__device__ inline void reduce_pairs(float* red, f32x4 s, f32x4 sx, int rg, int c4, float* __restrict__ partials) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) { red[(rg * 2 + 0) * H1 + c4 + u] = s[u]; red[(rg * 2 + 1) * H1 + c4 + u] = sx[u]; }
+    __syncthreads();
+    if (32 * GROUPS == 2 * H1 || tid < 2 * H1) {
+        float t = 0.f;
+#pragma unroll
+        for (int k = 0; k < GROUPS; ++k) t += red[k * 2 * H1 + tid];
+        partials[(size_t)blockIdx.x * 2 * H1 + tid] = t;
+    }
+}
+
 // ---- backward of the second layers ------------------------------------------------------------------------------------------
 // per 64-row tile: dz2 = gamma2 invstd2 (g2 - mean(g2) - xhat2 mean(g2 xhat2));  dW2[head] += dz2^T h1 (K = rows, MFMA);
 // dh1 = dz2 W2 (MFMA), written as whole rows.  tot = the reduced sums of k_cls_out_bwd_sums (double).
-// (3 waves per SIMD = the 3 workgroups per CU the 768-block grid counts on: 150 VGPRs, no spills; left to itself the
-//  compiler took 182 and the third of the grid that was not resident ran as a tail: 1.06 -> 0.71 ms at B = 32)
-#ifndef MID_BWD_WGS
-#define MID_BWD_WGS 2               // workgroups per CU (register budget 256 / 168 VGPRs for 2 / 3)
-#endif
+constexpr int MID_BWD_WGS = 2;      // workgroups per CU: the launch bound, and with it the grid cap 256 * MID_BWD_WGS = 512 (all resident at once)
 // MASKED: what is written is g1 = dh1 * mask1 (the masked gradient the first layers' BatchNorm backward starts from -- this kernel
 // forms it anyway for its sums), so that k_cls_first_bwd need not regenerate the dropout / ReLU mask per element.
 template <bool MASKED>
@@ -572,11 +555,7 @@ __global__ __launch_bounds__(CT_THREADS, MID_BWD_WGS) void k_cls_mid_bwd(const f
 #pragma unroll
                     for (int u = 0; u < 4; ++u) v[u] = fmaxf(v[u], 0.f);
                     if (d1.p > 0.f) {
-#ifdef EG_ABL_HASH_MID        // (timing-only)
-                        const f32x4 kk = f32x4{d1.inv_keep, 0.f, d1.inv_keep, 0.f};
-#else
                         const f32x4 kk = keep_scale4(d1.seed, (unsigned long long)(row0 + r) * H1 + c4, d1.p, d1.inv_keep);
-#endif
                         v *= kk;
 #pragma unroll
                         for (int u = 0; u < 4; ++u) keep1 |= (kk[u] != 0.f ? 1u : 0u) << (4 * it + u);
@@ -597,12 +576,8 @@ __global__ __launch_bounds__(CT_THREADS, MID_BWD_WGS) void k_cls_mid_bwd(const f
                 const f32x4 mn = *reinterpret_cast<const f32x4*>(bn2.mean + c4), is = *reinterpret_cast<const f32x4*>(bn2.invstd + c4);
                 const f32x4 sc = *reinterpret_cast<const f32x4*>(bn2.scale + c4), sh = *reinterpret_cast<const f32x4*>(bn2.shift + c4);
                 const f32x4 ww = *reinterpret_cast<const f32x4*>(w3 + c4);
-#ifdef EG_ABL_HASH_MID
-                const f32x4 kk = f32x4{d2.inv_keep, 0.f, d2.inv_keep, 0.f}; (void)row;
-#else
                 const f32x4 kk = d2.p > 0.f ? keep_scale4(d2.seed, (unsigned long long)row * H2 + c4, d2.p, d2.inv_keep)
                                             : f32x4{1.f, 1.f, 1.f, 1.f};
-#endif
                 float ov[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
@@ -679,17 +654,7 @@ __global__ __launch_bounds__(CT_THREADS, MID_BWD_WGS) void k_cls_mid_bwd(const f
         }
         __syncthreads();
     }
-    {   // per-block partial [2][128]: the 8 threads that share a channel group are added in a fixed order
-        float* red = s_h;                                                     // [8][2][128]
-        const int rg = tid >> 5;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { red[(rg * 2 + 0) * H1 + c4s + u] = sg1[u]; red[(rg * 2 + 1) * H1 + c4s + u] = sx1[u]; }
-        __syncthreads();
-        float t = 0.f;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) t += red[k * 2 * H1 + tid];
-        partial_bn1[(size_t)blockIdx.x * 2 * H1 + tid] = t;                    // tid < 256 = 2 * 128
-    }
+    reduce_pairs<CT_THREADS / 32>(s_h, sg1, sx1, tid >> 5, c4s, partial_bn1);      // (s_h: the tile loop ends with a barrier)
     // per-block dW2 partial [4][16][32]: lane (i = l & 15, q), reg e -> [head][4 q + e][16 ib + i]
     float* p = partial_dw2 + (size_t)blockIdx.x * (4 * 16 * 32) + head * 512;
 #pragma unroll
@@ -727,11 +692,59 @@ struct FirstBwdArgs {
     int direct;                                              // both below 2 GB: buffer accesses off whole-array descriptors
 };
 
-#ifndef FB_ABL
-#define FB_ABL 0            // timing-only ablations (bits): 1 no weight-gradient product, 2 no dh product; direct form also: 4 no dz1 arithmetic,
-#endif                      // 8 no dh store, 16 no LDS tile writes, 32 no row loads, 64 no layer sums
+// Per-channel constants of the kernel in LDS: s_c [FC_COUNT][128], written once by k_cls_first_bwd; slot s of the thread's 4
+// channels is the float4 at s_c + s * H1 + c4.
+enum FbConst {
+    FC_MEAN, FC_INVSTD, FC_GAMMA, FC_BETA,          // the first layers' BatchNorm
+    FC_MEAN_G, FC_MEAN_GX,                          // mean g1, mean g1 xhat1 (tot / rows)
+    FC_LMEAN, FC_LINVSTD, FC_LGAMMA, FC_LBETA,      // SUMS: the layer's BatchNorm
+    FC_LSCALE, FC_LSHIFT,                           // ... and its forward scale / shift (hrec; 1, 0 otherwise)
+    FC_COUNT
+};
+
+// ---- what the two addressing forms below share ---------------------------------------------------------------------------
 // The two roles run separate instantiations of the tile loop (so that neither carries the other's persistent registers: the
 // [32 x 128] accumulators of the weight gradient / the W1 slice); both execute the same two workgroup barriers per tile.
+// Shared as functions: the layer-sums element step, the block partial of those sums (reduce_pairs) and the dW1 slab store.  The
+// role set-up, the two products and the dz1 expression are written out in both loops: behind a call boundary -- as a struct with
+// member functions, as free functions over the register arrays, by value or by reference -- each of them moved the instruction
+// stream of the direct form (profiles/cls_train_refactor_codeobj.txt), and that stream is what the kernel's time is made of.
+// A change to one of those three is made in both loops.
+
+// the workgroup's dW1 slab (waves 0..3)
+__device__ inline void fb_store_dw1(float* partial_dw1, int wave, int lane_k, const f32x16 (&acc)[4]) {
+    const int i = lane_k & 31, kh = lane_k >> 5;
+    float* p = partial_dw1 + (size_t)blockIdx.x * C * C;
+#pragma unroll
+    for (int jb = 0; jb < 4; ++jb)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int m = (e & 3) + 8 * (e >> 2) + 4 * kh;
+            p[(size_t)(32 * wave + m) * C + 32 * jb + i] = acc[jb][e];
+        }
+}
+
+// SUMS, one float4 of dh on its way out: k_bn_bwd_partial's expression per element (train.hip).  g: dh times the layer's dropout
+// scale (how the mask is had differs between the forms); z: the layer's z of the same elements.
+struct LayerSumConsts {
+    f32x4 lm, li, lg, lb;
+    __device__ inline LayerSumConsts(const float* s_c, int c4)
+        : lm(*reinterpret_cast<const f32x4*>(s_c + FC_LMEAN * H1 + c4)), li(*reinterpret_cast<const f32x4*>(s_c + FC_LINVSTD * H1 + c4)),
+          lg(*reinterpret_cast<const f32x4*>(s_c + FC_LGAMMA * H1 + c4)), lb(*reinterpret_cast<const f32x4*>(s_c + FC_LBETA * H1 + c4)) {}
+};
+__device__ inline void layer_sums_step(const f32x4& g, const f32x4& z, const LayerSumConsts& k, int relu, f32x4& lsg, f32x4& lsx) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const float xh = (z[u] - k.lm[u]) * k.li[u];
+        const float v = xh * k.lg[u] + k.lb[u];
+        float ge = g[u];
+        if (relu) ge = v > 0.f ? ge : 0.f;
+        lsg[u] += ge;
+        lsx[u] += ge * xh;
+    }
+}
+
+// ---- FLAT form: flat 32-bit element offsets, a bounds test per row, the layer's z rows (SUMS) prefetched with the others ------
 template <bool GEMM2, bool SUMS>
 __device__ inline void first_bwd_role_flat(const FirstBwdArgs& a, float* s_g, float* s_x, float* s_o, const float* s_c, int wave) {
     const int tid = threadIdx.x, lane_k = tid & 63;
@@ -787,9 +800,9 @@ __device__ inline void first_bwd_role_flat(const FirstBwdArgs& a, float* s_g, fl
         asm volatile("" : "+v"(lane));
         const long long r0 = t * TILE;
         {
-            const f32x4 mn = *reinterpret_cast<const f32x4*>(s_c + 0 * H1 + c4), is = *reinterpret_cast<const f32x4*>(s_c + 1 * H1 + c4);
-            const f32x4 ga = *reinterpret_cast<const f32x4*>(s_c + 2 * H1 + c4), be = *reinterpret_cast<const f32x4*>(s_c + 3 * H1 + c4);
-            const f32x4 mg = *reinterpret_cast<const f32x4*>(s_c + 4 * H1 + c4), mgx = *reinterpret_cast<const f32x4*>(s_c + 5 * H1 + c4);
+            const f32x4 mn = *reinterpret_cast<const f32x4*>(s_c + FC_MEAN * H1 + c4), is = *reinterpret_cast<const f32x4*>(s_c + FC_INVSTD * H1 + c4);
+            const f32x4 ga = *reinterpret_cast<const f32x4*>(s_c + FC_GAMMA * H1 + c4), be = *reinterpret_cast<const f32x4*>(s_c + FC_BETA * H1 + c4);
+            const f32x4 mg = *reinterpret_cast<const f32x4*>(s_c + FC_MEAN_G * H1 + c4), mgx = *reinterpret_cast<const f32x4*>(s_c + FC_MEAN_GX * H1 + c4);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int rl = (tid >> 5) + 16 * q;
@@ -823,7 +836,6 @@ __device__ inline void first_bwd_role_flat(const FirstBwdArgs& a, float* s_g, fl
         if (t + gridDim.x < n_tiles) issue(t + gridDim.x);
         if constexpr (!GEMM2) {
             const int i = lane & 31, kh = lane >> 5;
-            if (!(FB_ABL & 1))
 #pragma unroll 4
             for (int s = 0; s < TILE / 2; ++s) {
                 const int r = 2 * s + kh;
@@ -839,7 +851,7 @@ __device__ inline void first_bwd_role_flat(const FirstBwdArgs& a, float* s_g, fl
                 f32x16 o;
 #pragma unroll
                 for (int e = 0; e < 16; ++e) o[e] = 0.f;
-                if (!(FB_ABL & 2)) mfma_rowblock(s_g, 32 * rb, lane, wreg, o);
+                mfma_rowblock(s_g, 32 * rb, lane, wreg, o);
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
                     *reinterpret_cast<f32x4*>(&s_o[(32 * rb + j) * LDA + 32 * w + 4 * hh + 8 * g]) = f32x4{o[4 * g], o[4 * g + 1], o[4 * g + 2], o[4 * g + 3]};
@@ -857,20 +869,11 @@ __device__ inline void first_bwd_role_flat(const FirstBwdArgs& a, float* s_g, fl
                     const unsigned hoff = mapped(f0, in0, rl) * (unsigned)C + (unsigned)c4;
                     const f32x4 dv = *reinterpret_cast<const f32x4*>(&s_o[rl * LDA + c4]);
                     *reinterpret_cast<f32x4*>(a.dh + hoff) = dv;
-                    if (SUMS) {                   // k_bn_bwd_partial's expression per element (train.hip), on the row just written
-                        const f32x4 lm = *reinterpret_cast<const f32x4*>(s_c + 6 * H1 + c4), li = *reinterpret_cast<const f32x4*>(s_c + 7 * H1 + c4);
-                        const f32x4 lg = *reinterpret_cast<const f32x4*>(s_c + 8 * H1 + c4), lb = *reinterpret_cast<const f32x4*>(s_c + 9 * H1 + c4);
+                    if (SUMS) {                   // on the row just written
+                        const LayerSumConsts lk(s_c, c4);
                         f32x4 g = dv;
                         if (a.la.p > 0.f) g *= keep_scale4(a.la.seed, (unsigned long long)hoff, a.la.p, a.la.inv_keep);
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            const float xh = (cl[q][u] - lm[u]) * li[u];
-                            const float v = xh * lg[u] + lb[u];
-                            float ge = g[u];
-                            if (a.la.relu) ge = v > 0.f ? ge : 0.f;
-                            lsg[u] += ge;
-                            lsx[u] += ge * xh;
-                        }
+                        layer_sums_step(g, cl[q], lk, a.la.relu, lsg, lsx);
                     }
                 }
             }
@@ -878,33 +881,13 @@ __device__ inline void first_bwd_role_flat(const FirstBwdArgs& a, float* s_g, fl
     }
     if constexpr (SUMS) {                         // the 16 threads that share a channel group (both roles), in a fixed order
         __syncthreads();
-        float* red = s_g;                         // [16][2][128]
-        const int rg = tid >> 5;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { red[(rg * 2 + 0) * H1 + c4 + u] = lsg[u]; red[(rg * 2 + 1) * H1 + c4 + u] = lsx[u]; }
-        __syncthreads();
-        if (tid < 2 * H1) {
-            float t = 0.f;
-#pragma unroll
-            for (int k = 0; k < 16; ++k) t += red[k * 2 * H1 + tid];
-            a.partial_lsums[(size_t)blockIdx.x * 2 * H1 + tid] = t;
-        }
+        reduce_pairs<16>(s_g, lsg, lsx, tid >> 5, c4, a.partial_lsums);
         __syncthreads();
     }
-    if constexpr (!GEMM2) {
-        const int i = lane_k & 31, kh = lane_k >> 5;
-        float* p = a.partial_dw1 + (size_t)blockIdx.x * C * C;
-#pragma unroll
-        for (int jb = 0; jb < 4; ++jb)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int m = (e & 3) + 8 * (e >> 2) + 4 * kh;
-                p[(size_t)(32 * wave + m) * C + 32 * jb + i] = acc[jb][e];
-            }
-    }
+    if constexpr (!GEMM2) fb_store_dw1(a.partial_dw1, wave, lane_k, acc);
 }
 
-// DIRECT form (the arrays below 2 GB each -- batch 32 at 224/7 has 1.2 GB -- else the flat-address form above).
+// ---- DIRECT form (the arrays below 2 GB each -- batch 32 at 224/7 has 1.2 GB -- else the flat form above).
 // Every vector instruction of a tile serialises with the SIMD's MFMAs (running the two roles half a period apart, so
 // that each SIMD always had one wave in its chain and one wave on the tile's other work, changed nothing:
 // profiles/r05_heads_bwd_stagger_ab.txt), so what the tile costs beside its 256 MFMAs per SIMD is its instruction COUNT.  Here the
@@ -955,7 +938,6 @@ __device__ inline void first_bwd_role_direct(const FirstBwdArgs& a, float* s_g, 
         return T.brk >= TILE ? v : (rl0 + 16 * q >= T.brk ? v + gap : v);
     };
     auto issue = [&](const Tile& T) {
-        if (FB_ABL & 32) return;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             pd[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_d, voff0 + q * QB, T.soff_c, 0));
@@ -971,21 +953,9 @@ __device__ inline void first_bwd_role_direct(const FirstBwdArgs& a, float* s_g, 
             for (int q = 0; q < 4; ++q) pl[SUMS ? q : 0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_l, vm(T, q), T.soff_m, 0));
         }
     }
-#ifdef FB_STAMP              // (diagnostic build: cycles per phase, summed over the workgroup's tiles, printed by two waves of workgroup 0)
-    unsigned long long st[7] = {0, 0, 0, 0, 0, 0, 0};
-#define FB_T0 unsigned long long t_prev_ = __builtin_readcyclecounter();
-#define FB_MARK(k) do { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); const unsigned long long now_ = __builtin_readcyclecounter(); st[k] += now_ - t_prev_; t_prev_ = now_; } while (0)
-#define FB_MARK_NOWAIT(k) do { const unsigned long long now_ = __builtin_readcyclecounter(); st[k] += now_ - t_prev_; t_prev_ = now_; } while (0)
-#else
-#define FB_T0
-#define FB_MARK(k) do {} while (0)
-#define FB_MARK_NOWAIT(k) do {} while (0)
-#endif
     for (int t = blockIdx.x; t < n_tiles; t += gridDim.x) {
         int lane = lane_k;
         asm volatile("" : "+v"(lane));
-        FB_T0
-        FB_MARK(0);                               // wait for the prefetched rows
         const bool ragged = (t + 1) * TILE > rows;            // the array's last tile: rows past the end must not reach the sums
         unsigned lkeep = 0xFFFFu;              // the layer's dropout mask over this thread's 4 x 4 elements of the tile: hashed once, used
         if (SUMS && a.la.p > 0.f) {            // for the rebuilt h here and for the gate of the sums where dh leaves the tile
@@ -998,7 +968,7 @@ __device__ inline void first_bwd_role_direct(const FirstBwdArgs& a, float* s_g, 
         if (SUMS && a.hrec) {
             // the layer's output h = act(z) + residual was never written (k_act_lin128 h_skip_*): rebuilt here from the z rows this tile
             // holds for its sums anyway and the residual rows (prefetched in h's place), with the forward's own expression and mask
-            const f32x4 lsc = *reinterpret_cast<const f32x4*>(s_c + 10 * H1 + c4), lsh = *reinterpret_cast<const f32x4*>(s_c + 11 * H1 + c4);
+            const f32x4 lsc = *reinterpret_cast<const f32x4*>(s_c + FC_LSCALE * H1 + c4), lsh = *reinterpret_cast<const f32x4*>(s_c + FC_LSHIFT * H1 + c4);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 f32x4 v = pl[SUMS ? q : 0] * lsc + lsh;
@@ -1008,16 +978,15 @@ __device__ inline void first_bwd_role_direct(const FirstBwdArgs& a, float* s_g, 
             }
         }
         {
-            const f32x4 mn = *reinterpret_cast<const f32x4*>(s_c + 0 * H1 + c4), is = *reinterpret_cast<const f32x4*>(s_c + 1 * H1 + c4);
-            const f32x4 ga = *reinterpret_cast<const f32x4*>(s_c + 2 * H1 + c4), be = *reinterpret_cast<const f32x4*>(s_c + 3 * H1 + c4);
-            const f32x4 mg = *reinterpret_cast<const f32x4*>(s_c + 4 * H1 + c4), mgx = *reinterpret_cast<const f32x4*>(s_c + 5 * H1 + c4);
+            const f32x4 mn = *reinterpret_cast<const f32x4*>(s_c + FC_MEAN * H1 + c4), is = *reinterpret_cast<const f32x4*>(s_c + FC_INVSTD * H1 + c4);
+            const f32x4 ga = *reinterpret_cast<const f32x4*>(s_c + FC_GAMMA * H1 + c4), be = *reinterpret_cast<const f32x4*>(s_c + FC_BETA * H1 + c4);
+            const f32x4 mg = *reinterpret_cast<const f32x4*>(s_c + FC_MEAN_G * H1 + c4), mgx = *reinterpret_cast<const f32x4*>(s_c + FC_MEAN_GX * H1 + c4);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int rl = rl0 + 16 * q;
                 f32x4 vg;
                 f32x4 d = pd[q];
-                if (FB_ABL & 4) vg = d + pz[q];
-                else if (a.masked) {
+                if (a.masked) {
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
                         const float xh = (pz[q][u] - mn[u]) * is[u];
@@ -1034,20 +1003,16 @@ __device__ inline void first_bwd_role_direct(const FirstBwdArgs& a, float* s_g, 
                     }
                 }
                 if (ragged && t * TILE + rl >= rows) vg = f32x4{0.f, 0.f, 0.f, 0.f};      // (as the flat form: a missing row is a zero row)
-                if (!(FB_ABL & 16)) {
-                    *reinterpret_cast<f32x4*>(&s_g[rl * LDA + c4]) = vg;
-                    *reinterpret_cast<f32x4*>(&s_x[rl * LDA + c4]) = px[q];
-                } else asm volatile("" :: "v"(vg.x), "v"(vg.y), "v"(vg.z), "v"(vg.w), "v"(px[q].x), "v"(px[q].y), "v"(px[q].z), "v"(px[q].w));
+                *reinterpret_cast<f32x4*>(&s_g[rl * LDA + c4]) = vg;
+                *reinterpret_cast<f32x4*>(&s_x[rl * LDA + c4]) = px[q];
             }
         }
         __syncthreads();                          // tile in LDS; s_o of the tile before has been stored
         const bool more = t + (int)gridDim.x < n_tiles;      // (the loads in FRONT of this barrier instead: 2.40 -> 2.42 ms, profiles/r05_heads_bwd_ablations.txt)
         Tile Tn{0, 0, TILE};
         if (more) { Tn = tile_of(t + gridDim.x); issue(Tn); }
-        FB_MARK_NOWAIT(3);                        // issue
         if constexpr (!GEMM2) {
             const int i = lane & 31, kh = lane >> 5;
-            if (!(FB_ABL & 1))
 #pragma unroll 4
             for (int s = 0; s < TILE / 2; ++s) {
                 const int r = 2 * s + kh;
@@ -1063,15 +1028,13 @@ __device__ inline void first_bwd_role_direct(const FirstBwdArgs& a, float* s_g, 
                 f32x16 o;
 #pragma unroll
                 for (int e = 0; e < 16; ++e) o[e] = 0.f;
-                if (!(FB_ABL & 2)) mfma_rowblock(s_g, 32 * rb, lane, wreg, o);
+                mfma_rowblock(s_g, 32 * rb, lane, wreg, o);
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
                     *reinterpret_cast<f32x4*>(&s_o[(32 * rb + j) * LDA + 32 * w + 4 * hh + 8 * g]) = f32x4{o[4 * g], o[4 * g + 1], o[4 * g + 2], o[4 * g + 3]};
             }
         }
-        FB_MARK_NOWAIT(4);                        // products
         __syncthreads();                          // products done: s_g / s_x may be refilled, s_o is complete
-        FB_MARK_NOWAIT(5);                        // barrier 2
         {
             const Tile T = tile_of(t);
 #pragma unroll
@@ -1079,65 +1042,24 @@ __device__ inline void first_bwd_role_direct(const FirstBwdArgs& a, float* s_g, 
                 const int rl = rl0 + 16 * q;
                 const int vo = vm(T, q);
                 const f32x4 dv = *reinterpret_cast<const f32x4*>(&s_o[rl * LDA + c4]);
-                if (!(FB_ABL & 8)) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, dv), rs_o, vo, T.soff_m, 0);
-                if (SUMS && !(FB_ABL & 64) && !(ragged && t * TILE + rl >= rows)) {     // k_bn_bwd_partial's expression per element (train.hip), on the row just written
-                    const f32x4 lm = *reinterpret_cast<const f32x4*>(s_c + 6 * H1 + c4), li = *reinterpret_cast<const f32x4*>(s_c + 7 * H1 + c4);
-                    const f32x4 lg = *reinterpret_cast<const f32x4*>(s_c + 8 * H1 + c4), lb = *reinterpret_cast<const f32x4*>(s_c + 9 * H1 + c4);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, dv), rs_o, vo, T.soff_m, 0);
+                if (SUMS && !(ragged && t * TILE + rl >= rows)) {     // on the row just written
+                    const LayerSumConsts lk(s_c, c4);
                     f32x4 g = dv;
-#ifdef EG_ABL_HASH_FIRST      // (timing-only)
-                    g *= a.la.inv_keep;
-#else
                     if (a.la.p > 0.f) g *= keep_scale_of_bits(lkeep >> (4 * q), a.la.inv_keep);
-#endif
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const float xh = (pl[SUMS ? q : 0][u] - lm[u]) * li[u];
-                        const float v = xh * lg[u] + lb[u];
-                        float ge = g[u];
-                        if (a.la.relu) ge = v > 0.f ? ge : 0.f;
-                        lsg[u] += ge;
-                        lsx[u] += ge * xh;
-                    }
+                    layer_sums_step(g, pl[SUMS ? q : 0], lk, a.la.relu, lsg, lsx);
                 }
                 asm volatile("s_nop 1" :: "v"(dv.x), "v"(dv.y), "v"(dv.z), "v"(dv.w) : "memory");       // (store data: DESIGN 5.26)
                 if (SUMS && more) pl[SUMS ? q : 0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_l, vm(Tn, q), Tn.soff_m, 0));
             }
         }
-        FB_MARK_NOWAIT(6);                        // store phase
     }
-#ifdef FB_STAMP
-    if (blockIdx.x == 7 && (tid & 63) == 0 && (wave == 0 || wave == 4 || wave == 3))
-        printf("wave %d tiles %d  wait-loads %llu build %llu bar1 %llu issue %llu products %llu bar2 %llu store %llu  (cycles per tile)\n", wave,
-               (n_tiles - 7 + (int)gridDim.x - 1) / (int)gridDim.x, st[0] * (unsigned long long)gridDim.x / n_tiles, st[1] * (unsigned long long)gridDim.x / n_tiles,
-               st[2] * (unsigned long long)gridDim.x / n_tiles, st[3] * (unsigned long long)gridDim.x / n_tiles, st[4] * (unsigned long long)gridDim.x / n_tiles,
-               st[5] * (unsigned long long)gridDim.x / n_tiles, st[6] * (unsigned long long)gridDim.x / n_tiles);
-#endif
     if constexpr (SUMS) {                         // the 16 threads that share a channel group (both roles), in a fixed order
         __syncthreads();
-        float* red = s_g;                         // [16][2][128]
-        const int rg = tid >> 5;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { red[(rg * 2 + 0) * H1 + c4 + u] = lsg[u]; red[(rg * 2 + 1) * H1 + c4 + u] = lsx[u]; }
-        __syncthreads();
-        if (tid < 2 * H1) {
-            float t = 0.f;
-#pragma unroll
-            for (int k = 0; k < 16; ++k) t += red[k * 2 * H1 + tid];
-            a.partial_lsums[(size_t)blockIdx.x * 2 * H1 + tid] = t;
-        }
+        reduce_pairs<16>(s_g, lsg, lsx, tid >> 5, c4, a.partial_lsums);
         __syncthreads();
     }
-    if constexpr (!GEMM2) {
-        const int i = lane_k & 31, kh = lane_k >> 5;
-        float* p = a.partial_dw1 + (size_t)blockIdx.x * C * C;
-#pragma unroll
-        for (int jb = 0; jb < 4; ++jb)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int m = (e & 3) + 8 * (e >> 2) + 4 * kh;
-                p[(size_t)(32 * wave + m) * C + 32 * jb + i] = acc[jb][e];
-            }
-    }
+    if constexpr (!GEMM2) fb_store_dw1(a.partial_dw1, wave, lane_k, acc);
 }
 
 template <bool SUMS, bool DIRECT>
@@ -1149,23 +1071,23 @@ __global__ __launch_bounds__(512) void k_cls_first_bwd(const FirstBwdArgs a_, co
     float* s_g = fb_smem;                         // [64][LDA]  dz1 tile
     float* s_x = fb_smem + TILE * LDA;            // [64][LDA]  h tile (valid rows)
     float* s_o = fb_smem + 2 * TILE * LDA;        // [64][LDA]  dh tile on its way out
-    float* s_c = fb_smem + 3 * TILE * LDA;        // [6 | 12][128]   mean, invstd, gamma, beta, mean g, mean g xhat (+ SUMS: the layer's mean, invstd, gamma, beta, scale, shift)
+    float* s_c = fb_smem + 3 * TILE * LDA;        // [FC_COUNT][128]  per-channel constants (the SUMS slots are written with SUMS only)
     const int tid = threadIdx.x, wave = wave_id();
     if (tid < H1) {
         const double inv_n = 1.0 / (double)a.rows;
-        s_c[0 * H1 + tid] = bn1.mean[tid];
-        s_c[1 * H1 + tid] = bn1.invstd[tid];
-        s_c[2 * H1 + tid] = bn1.gamma[tid];
-        s_c[3 * H1 + tid] = beta1[tid];
-        s_c[4 * H1 + tid] = (float)(a.tot[tid] * inv_n);
-        s_c[5 * H1 + tid] = (float)(a.tot[H1 + tid] * inv_n);
+        s_c[FC_MEAN * H1 + tid] = bn1.mean[tid];
+        s_c[FC_INVSTD * H1 + tid] = bn1.invstd[tid];
+        s_c[FC_GAMMA * H1 + tid] = bn1.gamma[tid];
+        s_c[FC_BETA * H1 + tid] = beta1[tid];
+        s_c[FC_MEAN_G * H1 + tid] = (float)(a.tot[tid] * inv_n);
+        s_c[FC_MEAN_GX * H1 + tid] = (float)(a.tot[H1 + tid] * inv_n);
         if (SUMS) {
-            s_c[6 * H1 + tid] = a.lmean[tid];
-            s_c[7 * H1 + tid] = a.linvstd[tid];
-            s_c[8 * H1 + tid] = a.lgamma[tid];
-            s_c[9 * H1 + tid] = a.lbeta[tid];
-            s_c[10 * H1 + tid] = a.hrec ? a.lscale[tid] : 1.f;
-            s_c[11 * H1 + tid] = a.hrec ? a.lshift[tid] : 0.f;
+            s_c[FC_LMEAN * H1 + tid] = a.lmean[tid];
+            s_c[FC_LINVSTD * H1 + tid] = a.linvstd[tid];
+            s_c[FC_LGAMMA * H1 + tid] = a.lgamma[tid];
+            s_c[FC_LBETA * H1 + tid] = a.lbeta[tid];
+            s_c[FC_LSCALE * H1 + tid] = a.hrec ? a.lscale[tid] : 1.f;
+            s_c[FC_LSHIFT * H1 + tid] = a.hrec ? a.lshift[tid] : 0.f;
         }
     }
     __syncthreads();
@@ -1271,9 +1193,26 @@ extern "C" {
 
 // workspace layout (bytes): [0, 8 MB) float partial slabs; then 4096 doubles of totals; eg_bn_act_bwd / dweight use the
 // region from offset CLS_WS_SHARED on (eg_workspace_bytes() bytes)
-static const size_t CLS_WS_PARTIAL = (size_t)CT_MAX_BLOCKS * 2048 * sizeof(float);
-static const size_t CLS_WS_TOTALS = 4096 * sizeof(double);
-static const size_t CLS_WS_SHARED = CLS_WS_PARTIAL + CLS_WS_TOTALS;
+constexpr size_t CLS_WS_PARTIAL = (size_t)CT_MAX_BLOCKS * 2048 * sizeof(float);
+constexpr size_t CLS_WS_TOTALS = 4096 * sizeof(double);
+constexpr size_t CLS_WS_SHARED = CLS_WS_PARTIAL + CLS_WS_TOTALS;
+// ... the float slabs of the backward, in floats (the forward's two slab arrays both start at 0: its reductions run in between):
+constexpr int MID_FWD_GRID = 768, MID_BWD_GRID = 256 * MID_BWD_WGS;            // grid caps of k_cls_mid_fwd / k_cls_mid_bwd
+constexpr int DW2_SLAB = 4 * 16 * 32, DW2_MAX_SLABS = 768;                     // (the cap k_cls_mid_bwd once had: the offset behind it stays)
+constexpr size_t WS_OUT_SUMS = 0;                                              // [CT_MAX_BLOCKS][OUT_SUMS]   k_cls_out_bwd_sums
+constexpr size_t WS_DW2 = WS_OUT_SUMS + (size_t)CT_MAX_BLOCKS * OUT_SUMS;      // [DW2_MAX_SLABS][DW2_SLAB]   k_cls_mid_bwd
+constexpr size_t WS_BN1 = WS_DW2 + (size_t)DW2_MAX_SLABS * DW2_SLAB;           // [MID_BWD_GRID][2][128]      k_cls_mid_bwd, then k_cls_first_bwd's layer sums
+constexpr size_t WS_PARTIAL_END = WS_BN1 + (size_t)MID_BWD_GRID * 2 * H1;
+static_assert(DW2_MAX_SLABS >= MID_BWD_GRID && MID_BWD_GRID >= FB_BLOCKS, "a slab per workgroup");
+static_assert(WS_PARTIAL_END * sizeof(float) <= CLS_WS_PARTIAL, "the backward's partial slabs fit");
+static_assert((size_t)LIN_GRID * 2 * H1 * sizeof(float) <= CLS_WS_PARTIAL && (size_t)MID_FWD_GRID * 2 * H2 * sizeof(float) <= CLS_WS_PARTIAL,
+              "the forward's partial slabs fit");
+// ... and the totals, in doubles
+constexpr size_t TOT_FIRST = 0;                       // forward: sums of z1 [2][128]; backward: the third layers' [OUT_SUMS]
+constexpr size_t TOT_SECOND = 256;                    // forward: sums of z2 [2][64]  (backward: [DW2_SLAB] kept free, k_cls_mid_final writes dW2 itself)
+constexpr size_t TOT_BN1 = TOT_SECOND + DW2_SLAB;     // backward: sum g1, sum g1 xhat1 [2][128]
+static_assert(OUT_SUMS <= TOT_SECOND - TOT_FIRST && 2 * H1 <= TOT_SECOND - TOT_FIRST && 2 * H2 <= DW2_SLAB, "the totals' regions do not overlap");
+static_assert((TOT_BN1 + 2 * H1) * sizeof(double) <= CLS_WS_TOTALS, "the totals fit");
 
 size_t eg_classifier_train_workspace_bytes(void) { return CLS_WS_SHARED + eg_workspace_bytes(); }
 
@@ -1300,19 +1239,18 @@ static int classifier_train_fwd(const float* h, const LinAct* act, int batch, in
     const long long n_tiles = (long long)d.tiles_per_frame * batch;
     if (n_tiles >= (1ll << 31)) return set_error(EG_ERR_ARG, "too many row tiles");
     const int g1 = (int)(n_tiles < LIN_GRID ? n_tiles : LIN_GRID);
-    // (round 4's 8-wave form k_lin128_map<true, true> lost every A/B against the 4-wave k_act_lin128 and is no longer reachable)
     if (act) hipLaunchKernelGGL(k_act_lin128, dim3(g1), dim3(256), 0, stream, P->w1, P->b1, z1, partial, d, *act);
-    else hipLaunchKernelGGL((k_lin128_map<true, false>), dim3(g1), dim3(512), 0, stream, h, P->w1, P->b1, z1, partial, d, LinAct{});
-    BnFinalize f1{totals, rows, H1, P->gamma1, P->beta1, P->eps1, P->momentum1, P->running_mean1, P->running_var1,
+    else hipLaunchKernelGGL(k_lin128_map<true>, dim3(g1), dim3(512), 0, stream, h, P->w1, P->b1, z1, partial, d);
+    BnFinalize f1{totals + TOT_FIRST, rows, H1, P->gamma1, P->beta1, P->eps1, P->momentum1, P->running_mean1, P->running_var1,
                   bn + 0 * H1, bn + 1 * H1, bn + 2 * H1, bn + 3 * H1};
     hipLaunchKernelGGL(k_bn_reduce_finalize, dim3(H1 / 16), dim3(RED_F32_THREADS), 0, stream, (const float*)partial, g1, f1);
     // ---- second layers + BatchNorm1d(64) statistics
     float* bn2p = bn + 4 * H1;
     const ClsBn bn1{bn + 0 * H1, bn + 1 * H1, bn + 2 * H1, bn + 3 * H1, P->gamma1};
     const ClsDrop d1{P->p1, P->p1 > 0.f ? 1.0f / (1.0f - P->p1) : 1.0f, P->seed1, eg_epoch_ptr()};
-    const int g2 = grid_for(rows, TILE, 768);
+    const int g2 = grid_for(rows, TILE, MID_FWD_GRID);
     hipLaunchKernelGGL(k_cls_mid_fwd, dim3(g2), dim3(CT_THREADS), 0, stream, z1, rows, P->w2, P->b2, bn1, d1, z2, partial);
-    BnFinalize f2{totals + 256, rows, H2, P->gamma2, P->beta2, P->eps2, P->momentum2, P->running_mean2, P->running_var2,
+    BnFinalize f2{totals + TOT_SECOND, rows, H2, P->gamma2, P->beta2, P->eps2, P->momentum2, P->running_mean2, P->running_var2,
                   bn2p + 0 * H2, bn2p + 1 * H2, bn2p + 2 * H2, bn2p + 3 * H2};
     hipLaunchKernelGGL(k_bn_reduce_finalize, dim3(H2 / 16), dim3(RED_F32_THREADS), 0, stream, (const float*)partial, g2, f2);
     // ---- third layers
@@ -1356,6 +1294,18 @@ struct LayerSumsReq {               // eg_classifier_bwd_sums: the layer in fron
     int recompute_h;                // h was not written (eg_classifier_train_fwd_act h_sparse): the first-layers kernel rebuilds its tile
 };
 
+// both arrays ([batch * n_valid, 128] compact, [batch * n_per_frame, 128] unfiltered) below 2^31 - 2^20 bytes: 32-bit byte
+// offsets, a tile's overhang included -- what the buffer-descriptor form of k_cls_first_bwd needs
+static bool arrays_below_2gb(int batch, int64_t n_per_frame, int64_t n_valid) {
+    const long long lim = (1ll << 31) - (1ll << 20);
+    return (long long)batch * n_valid * (C * 4) < lim && (long long)batch * n_per_frame * (C * 4) < lim;
+}
+
+// k_cls_first_bwd [SUMS][DIRECT]
+typedef void (*FirstBwdKernel)(const FirstBwdArgs, const ClsBn, const float*);
+static const FirstBwdKernel FIRST_BWD[2][2] = {{k_cls_first_bwd<false, false>, k_cls_first_bwd<false, true>},
+                                               {k_cls_first_bwd<true, false>, k_cls_first_bwd<true, true>}};
+
 static bool first_bwd_covers(const float* dh, int batch, int64_t n_per_frame, int64_t n_valid) {
     const long long rows = (long long)batch * n_valid;
     return dh && n_valid >= TILE && (long long)batch * n_per_frame * C < (1ll << 32) && rows * C < (1ll << 32);
@@ -1374,7 +1324,7 @@ static int classifier_bwd(const float* dlogits, const float* h, int batch, int64
     if (ls && !first_bwd_covers(dh, batch, n_per_frame, n_valid))
         return set_error(EG_ERR_UNSUPPORTED, "the layer's sums come out of the fused first-layers kernel: dh wanted, n_valid >= 64, < 2^32 elements");
     // (decided before anything is launched: the recomputed h tile exists in the buffer-descriptor form of the kernel only)
-    if (hrec && !((long long)batch * n_valid * (C * 4) < (1ll << 31) - (1ll << 20) && (long long)batch * n_per_frame * (C * 4) < (1ll << 31) - (1ll << 20)))
+    if (hrec && !arrays_below_2gb(batch, n_per_frame, n_valid))
         return set_error(EG_ERR_UNSUPPORTED, "recompute_h needs arrays below 2 GB");
     hipStream_t stream = (hipStream_t)stream_;
     const long long rows = (long long)batch * n_valid;
@@ -1388,22 +1338,23 @@ static int classifier_bwd(const float* dlogits, const float* h, int batch, int64
     const ClsDrop d2{P->p2, P->p2 > 0.f ? 1.0f / (1.0f - P->p2) : 1.0f, P->seed2, eg_epoch_ptr()};
     // ---- third layers: sums
     const int ga = grid_for(rows * 4, CT_THREADS * 8, CT_MAX_BLOCKS);
-    hipLaunchKernelGGL(k_cls_out_bwd_sums, dim3(ga), dim3(CT_THREADS), 0, stream, dlogits, z2, rows, bn2, d2, P->w3, partial);
-    hipLaunchKernelGGL(k_reduce_f32_partials, dim3((OUT_SUMS + 31) / 32), dim3(RED_F32_THREADS), 0, stream, partial, ga, OUT_SUMS, totals);
+    hipLaunchKernelGGL(k_cls_out_bwd_sums, dim3(ga), dim3(CT_THREADS), 0, stream, dlogits, z2, rows, bn2, d2, P->w3, partial + WS_OUT_SUMS);
+    hipLaunchKernelGGL(k_reduce_f32_partials, dim3((OUT_SUMS + 31) / 32), dim3(RED_F32_THREADS), 0, stream, partial + WS_OUT_SUMS, ga, OUT_SUMS,
+                       totals + TOT_FIRST);
     // ---- second layers: dz2, dW2, dh1 -- and the sums of the first layers' BatchNorm backward over g1 = dh1 * mask1
-    const int gb = grid_for(rows, TILE, 256 * MID_BWD_WGS);
-    float* partial2 = partial + (size_t)CT_MAX_BLOCKS * OUT_SUMS;
-    float* partial_bn1 = partial2 + (size_t)768 * (4 * 16 * 32);               // [gb][2][128]
-    double* tot_bn1 = totals + 256 + 4 * 16 * 32;
+    const int gb = grid_for(rows, TILE, MID_BWD_GRID);
+    float* partial2 = partial + WS_DW2;
+    float* partial_bn1 = partial + WS_BN1;
+    double* tot_bn1 = totals + TOT_BN1;
     const RowMap xm{(int)n_valid, (int)n_per_frame, (int)row_lo};
     const bool fused = first_bwd_covers(dh, batch, n_per_frame, n_valid);
     const bool masked = fused;                        // the masked gradient is handed over (the unfused route below applies the mask itself)
     hipLaunchKernelGGL(masked ? k_cls_mid_bwd<true> : k_cls_mid_bwd<false>, dim3(gb), dim3(CT_THREADS), 0, stream, dlogits, z2, z1, rows,
-                       bn1, d1, bn2, d2, P->w2, P->w3, totals, dh1_scratch, partial2, partial_bn1);
+                       bn1, d1, bn2, d2, P->w2, P->w3, totals + TOT_FIRST, dh1_scratch, partial2, partial_bn1);
     {
-        const MidFinal mf{partial2, partial_bn1, gb, totals, tot_bn1, grads, (fused && n_valid < n_per_frame) ? dh : nullptr, batch, (int)n_per_frame,
+        const MidFinal mf{partial2, partial_bn1, gb, totals + TOT_FIRST, tot_bn1, grads, (fused && n_valid < n_per_frame) ? dh : nullptr, batch, (int)n_per_frame,
                           (int)row_lo, (int)n_valid};
-        hipLaunchKernelGGL(k_cls_mid_final, dim3(4 * 16 * 32 / 32 + 2 * H1 / 32 + 1), dim3(RED_F32_THREADS), 0, stream, mf);
+        hipLaunchKernelGGL(k_cls_mid_final, dim3(DW2_SLAB / 32 + 2 * H1 / 32 + 1), dim3(RED_F32_THREADS), 0, stream, mf);
     }
     EG_HIP_TRY(hipGetLastError());
     // ---- first layers: dz1 formed on the fly, dW1 = dz1^T h[valid rows] and dh[valid rows] = dz1 W1 in ONE kernel
@@ -1413,26 +1364,20 @@ static int classifier_bwd(const float* dlogits, const float* h, int batch, int64
             int dev = 0;
             EG_HIP_TRY(hipGetDevice(&dev));
             if (dev < 0 || dev >= 64 || !attr_set[dev].load(std::memory_order_acquire)) {
-                EG_HIP_TRY(hipFuncSetAttribute((const void*)k_cls_first_bwd<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                EG_HIP_TRY(hipFuncSetAttribute((const void*)k_cls_first_bwd<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                EG_HIP_TRY(hipFuncSetAttribute((const void*)k_cls_first_bwd<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                EG_HIP_TRY(hipFuncSetAttribute((const void*)k_cls_first_bwd<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                for (int i = 0; i < 4; ++i)
+                    EG_HIP_TRY(hipFuncSetAttribute((const void*)FIRST_BWD[i >> 1][i & 1], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
                 if (dev >= 0 && dev < 64) attr_set[dev].store(true, std::memory_order_release);
             }
         }
         const long long nt = (rows + TILE - 1) / TILE;
         const int nf = (int)(nt < FB_BLOCKS ? nt : FB_BLOCKS);
         float* slabs = (float*)((char*)shared + eg_workspace_bytes() - (size_t)FB_BLOCKS * C * C * sizeof(float));
-        const size_t lds = (size_t)(3 * TILE * LDA + 12 * H1) * sizeof(float);
+        const size_t lds = (size_t)(3 * TILE * LDA + FC_COUNT * H1) * sizeof(float);
         FirstBwdArgs fa{dh1_scratch, z1, h, P->w1, (const double*)tot_bn1, rows, xm, d1, dh, slabs, masked ? 1 : 0};
-        {
-            const long long bc = rows * (C * 4), bm = (long long)batch * n_per_frame * (C * 4);
-            fa.direct = bc < (1ll << 31) - (1ll << 20) && bm < (1ll << 31) - (1ll << 20);   // (32-bit offsets incl. a tile's overhang)
-            fa.bytes_c = fa.direct ? (unsigned)bc : 0u;
-            fa.bytes_m = fa.direct ? (unsigned)bm : 0u;
-        }
-        if (ls && ls->recompute_h) {
-            if (!fa.direct) return set_error(EG_ERR_UNSUPPORTED, "recompute_h needs arrays below 2 GB (the buffer-descriptor form of the kernel)");
+        fa.direct = arrays_below_2gb(batch, n_per_frame, n_valid);
+        fa.bytes_c = fa.direct ? (unsigned)(rows * (C * 4)) : 0u;
+        fa.bytes_m = fa.direct ? (unsigned)((long long)batch * n_per_frame * (C * 4)) : 0u;
+        if (hrec) {                                       // (refused above unless fa.direct)
             fa.h = ls->residual; fa.hrec = 1; fa.lscale = ls->bn + 2 * C; fa.lshift = ls->bn + 3 * C;
         }
         if (ls) {
@@ -1440,12 +1385,12 @@ static int classifier_bwd(const float* dlogits, const float* h, int batch, int64
             fa.la.rows = (long long)batch * n_per_frame; fa.la.relu = ls->relu; fa.la.p = ls->p;
             fa.la.inv_keep = ls->p > 0.f ? 1.0f / (1.0f - ls->p) : 1.0f; fa.la.seed = ls->seed; fa.la.epoch = eg_epoch_ptr();
             fa.partial_lsums = partial_bn1;                                       // (reduced into tot_bn1 already)
-            hipLaunchKernelGGL((fa.direct ? k_cls_first_bwd<true, true> : k_cls_first_bwd<true, false>), dim3(nf), dim3(512), lds, stream, fa, bn1, P->beta1);
+            hipLaunchKernelGGL(FIRST_BWD[1][fa.direct], dim3(nf), dim3(512), lds, stream, fa, bn1, P->beta1);
             // dW1 from the slabs and the layer's sums from the column partials: one launch
             hipLaunchKernelGGL(k_dweight_final, dim3(C * C / 32 + 2 * H1 / 32), dim3(RED_F32_THREADS), 0, stream, (const float*)slabs, nf, grads,
                                ExtraReduce{(const float*)partial_bn1, nf, 2 * H1, ls->sums});
         } else {
-            hipLaunchKernelGGL((fa.direct ? k_cls_first_bwd<false, true> : k_cls_first_bwd<false, false>), dim3(nf), dim3(512), lds, stream, fa, bn1, P->beta1);
+            hipLaunchKernelGGL(FIRST_BWD[0][fa.direct], dim3(nf), dim3(512), lds, stream, fa, bn1, P->beta1);
             hipLaunchKernelGGL(k_dweight_final, dim3(C * C / 32), dim3(RED_F32_THREADS), 0, stream, (const float*)slabs, nf, grads, ExtraReduce{});
         }
         EG_HIP_TRY(hipGetLastError());
@@ -1467,8 +1412,8 @@ static int classifier_bwd(const float* dlogits, const float* h, int batch, int64
     d.n_valid = (int)n_valid; d.tiles_per_frame = (int)((n_valid + TILE - 1) / TILE); d.batch = batch; d.transpose_w = 1;
     d.in_stride = (int)n_valid; d.in_lo = 0; d.out_stride = (int)n_per_frame; d.out_lo = (int)row_lo;
     const long long n_tiles = (long long)d.tiles_per_frame * batch;
-    hipLaunchKernelGGL((k_lin128_map<false, false>), dim3((unsigned)(n_tiles < LIN_GRID ? n_tiles : LIN_GRID)), dim3(512), 0, stream, dh1_scratch,
-                       P->w1, (const float*)nullptr, dh, (float*)nullptr, d, LinAct{});
+    hipLaunchKernelGGL(k_lin128_map<false>, dim3((unsigned)(n_tiles < LIN_GRID ? n_tiles : LIN_GRID)), dim3(512), 0, stream, dh1_scratch,
+                       P->w1, (const float*)nullptr, dh, (float*)nullptr, d);
     EG_HIP_TRY(hipGetLastError());
     return EG_OK;
 }

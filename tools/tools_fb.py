@@ -1,7 +1,9 @@
-"""The heads' backward (eg_classifier_bwd / eg_classifier_bwd_sums) alone at BASELINE configs[3]'s shape: time per call and
-sha256 digests of everything it returns -- run once per setting of EG_FB_STAGGER (the knob is read once per process) and
-compare the digests: the staggered kernel claims bit-identical results.
-    B=32 python tools/tools_fb.py            (small shapes for the bit comparison: SHAPES=1)"""
+"""The heads' backward (eg_classifier_bwd / eg_classifier_bwd_sums) alone: sha256 digests of everything it returns (dh, grads, and
+with the layer's sums: dh, grads, sums) on five small shapes, then time per call and the same digests at BASELINE configs[3]'s
+shape.  Run it once per library (ECHOGLAD_LIB=<path>, tools/lib_ab.sh alternates them) and compare: two builds that claim the same
+results print the same digests.
+    B=32,59 python tools/tools_fb.py         (B: batch sizes of the timed shape, default 32; 59 and up are the arrays past 2 GiB,
+                                              k_cls_first_bwd's flat-address form; FB_TIMING_ONLY=1 skips the small shapes)"""
 import hashlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -55,8 +57,9 @@ def case(B, n, lo, n_valid, timing):
                                                                                       layer=(lz, lbn, lgamma, lbeta, True, 0.5, 77))))
 
 
-print("EG_FB_STAGGER =", os.environ.get("EG_FB_STAGGER", "(default)"))
 if not os.environ.get("FB_TIMING_ONLY"):
     for B, n, lo, nv in ((2, 341, 0, 341), (3, 1000, 7, 901), (1, 72024, 0, 72020), (2, 5000, 4, 4993), (5, 70, 3, 64)):
         case(B, n, lo, nv, False)
-case(int(os.environ.get("B", "32")), 72024, 0, 72020, True)
+for B in os.environ.get("B", "32").split(","):
+    case(int(B), 72024, 0, 72020, True)
+    torch.cuda.empty_cache()
