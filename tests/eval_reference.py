@@ -16,6 +16,7 @@ import torch
 
 from coord_reference import FACTOR, ULP, Report                 # noqa: F401  (the rule: unchanged, re-exported for the tests)
 from train_reference import ahat, ahat_t, edges_of              # noqa: F401
+from train_reference import graph_types as _graph_types, topo_edges as _topo_edges
 from echoglad_amd.topology import HierTopology, TopologySpec
 
 C = 128
@@ -27,20 +28,15 @@ HEAD_KEYS = ("w1", "s1", "t1", "w2", "s2", "t2", "w3", "b3")    # the packed inf
 # ---------------------------------------------------------------------------
 # graphs
 # ---------------------------------------------------------------------------
-def _types(diag_main, diag_aux):
-    return ("grid-diagonal" if diag_main else "grid"), ("grid-diagonal" if diag_aux else "grid")
-
-
 @functools.lru_cache(maxsize=None)
 def topology(frame, naux, main_only=False, coord=False, conn=False, diag_main=False, diag_aux=False):
-    return HierTopology(TopologySpec(frame, naux, main_only, coord, conn, *_types(diag_main, diag_aux)))
+    return HierTopology(TopologySpec(frame, naux, main_only, coord, conn, *_graph_types(diag_main, diag_aux)))
 
 
-@functools.lru_cache(maxsize=None)
 def topo_edges(frame, naux, main_only=False, coord=False, conn=False, diag_main=False, diag_aux=False):
-    """train_reference.edges_of one frame of the topology, 'grid-diagonal' levels and connection nodes included."""
-    topo = topology(frame, naux, main_only, coord, conn, diag_main, diag_aux)
-    return edges_of(topo.edge_index(), topo.num_nodes)
+    """train_reference.edges_of one frame of the topology, 'grid-diagonal' levels and connection nodes included: the one
+    implementation is train_reference.topo_edges."""
+    return _topo_edges(frame, naux, main_only, coord, conn, diag_main, diag_aux)
 
 
 def transposed(E):

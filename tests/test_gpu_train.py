@@ -1013,12 +1013,14 @@ def _kernel_keep_mask(n_elements: int, cols: int, p: float, seed: int) -> torch.
     return m.reshape(n_elements // cols, cols).cpu()
 
 
-def test_whole_train_step_with_dropout_against_the_oracle_under_the_kernels_masks(capsys):
+@pytest.mark.parametrize("graph_type", ["grid", "grid-diagonal"])
+def test_whole_train_step_with_dropout_against_the_oracle_under_the_kernels_masks(graph_type, capsys):
     """One FULL training step with dropout p = 0.5 at every site (3 GNN layers, 3 coordinate MLPs x 2, 4 heads x 2) at 64 / 6 +
     coordinate graph, B = 2, pushed through the oracle with the masks the kernels generated: logits, coordinates and every
-    parameter gradient.  The seeds of every site are handed out by the model (dropout_seed_hook), the masks are regenerated from
-    them by the kernels' own hash on the device, and the oracle's Dropout modules are replaced by those masks.  Tolerances as in
-    test_cfg4_train_step_error_against_fp64...: logits / coordinates within 4 x the oracle's own fp32-vs-fp64 distance,
+    parameter gradient; on 4-neighbour levels and with both the main grid and the aux levels 'grid-diagonal' (the same nodes: the
+    one place where the kernels' masks meet a whole step on the {mode 1 / 2 / 3, diag} forms of the layer kernel).
+    The seeds of every site are handed out by the model (dropout_seed_hook), the masks are regenerated from them by the kernels'
+    own hash on the device, and the oracle's Dropout modules are replaced by those masks.  Tolerances as in test_cfg4_train_step_error_against_fp64...: logits / coordinates within 4 x the oracle's own fp32-vs-fp64 distance,
     gradients channel-wise (gpu_util.assert_param_grads_close: a ReLU kink flip moves one channel)."""
     from gpu_util import assert_param_grads_close
     frame, naux, L, B, p = 64, 6, 3, 2, 0.5
@@ -1028,8 +1030,9 @@ def test_whole_train_step_with_dropout_against_the_oracle_under_the_kernels_mask
                                            classifier_hidden_dim=32, use_coordinate_graph=True, output_activation="logit").double()
     ref64.load_state_dict({k: v.double() if v.is_floating_point() else v for k, v in ref.state_dict().items()})
     hip.train(); ref.train(); ref64.train()
-    topo, ei, nt, bi = graph_tensors(frame, naux, B, coord=True)
+    topo, ei, nt, bi = graph_tensors(frame, naux, B, coord=True, main_type=graph_type, aux_type=graph_type)
     n, n_valid = topo.num_nodes, topo.num_valid_nodes
+    assert n == graph_tensors(frame, naux, B, coord=True)[0].num_nodes
     feats = synthetic_node_feats(B * n, 128, seed=77)
     c0 = initial_coords(B, frame)
     seeds = {}
@@ -1039,6 +1042,8 @@ def test_whole_train_step_with_dropout_against_the_oracle_under_the_kernels_mask
     loss = (got ** 2).mean() + (gc ** 2).mean() * 1e-3
     loss.backward()
     # every site drew a seed, all different
+    graph, _ = hip._resolver.resolve(ei.to(DEV), B * n)
+    assert graph.structured and graph.hybrid == (graph_type == "grid-diagonal")
     flat = [s for v in seeds.values() for s in v]
     assert len(seeds) == L + L + 1 and len(set(flat)) == len(flat) == L + 2 * L + 2 and all(s > 0 for s in flat)
     layer_masks = [_kernel_keep_mask(B * n * 128, 128, p, seeds[("gnn", id(hip.gnn_layers[i]))][0]) for i in range(L)]
@@ -1066,7 +1071,7 @@ def test_whole_train_step_with_dropout_against_the_oracle_under_the_kernels_mask
     err_l = float((got.detach().cpu().double() - w64).abs().max())
     err_c = float((gc.detach().cpu().double() - c64).abs().max())
     with capsys.disabled():
-        print(f"\n  p = 0.5 train step vs fp64 oracle under the kernels' masks: logits |hip-fp64| {err_l:.3e} (oracle fp32: {ref_err_l:.3e}), "
+        print(f"\n  p = 0.5 train step on {graph_type!r} levels vs fp64 oracle under the kernels' masks: logits |hip-fp64| {err_l:.3e} (oracle fp32: {ref_err_l:.3e}), "
               f"coords {err_c:.3e} (oracle fp32: {ref_err_c:.3e})")
     assert err_l <= 4 * ref_err_l + 8 * ulp * float(w64.abs().max()), (err_l, ref_err_l)
     assert err_c <= 4 * ref_err_c + 8 * ulp * frame, (err_c, ref_err_c)

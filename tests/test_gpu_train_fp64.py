@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import coord_reference as CR
+import eval_reference as EV
 import train_reference as T
 from echoglad_amd import ops
 
@@ -51,6 +52,9 @@ def _graph(case):
     E, B, rows = T.layer_edges(case)
     if case[0] == "topo":
         g = ops.Graph.topo(case[1], case[2], case[3], case[4], use_connection_nodes=case[5])
+    elif case[0] == "diag":
+        g = ops.Graph.topo(case[1], case[2], case[3], case[4], use_connection_nodes=case[5], diag_main=case[6], diag_aux=case[7])
+        assert g.structured and g.hybrid
     else:
         g = ops.Graph.csr(torch.from_numpy(T.case_edge_index(case)).to(DEV), rows)
         assert not g.structured and g.kidsum_rows == 0
@@ -85,10 +89,29 @@ def _check_layer_backward(rep, tag, got, r64, r32, need_dx=True, need_dw=True):
     rep.check("dbeta" + tag, dbeta, r64["dbeta"], r32["dbeta"], r64["dbeta_scale"])
 
 
+def _check_child_sums(rep, tag, topo, B, ka, out, r64, r32):
+    """kidsum_out of a train forward under the rule, twice: against eval_reference.kidsum of the reference's out (float64, and float32
+    as the yardstick; the scale: the same sums over the scale `out` itself is judged with, its largest magnitude), and against
+    kidsum of the kernel's OWN out (the kernel sums its own rows: float64 sums of them, float32 sums as the yardstick, the sums of
+    their magnitudes as the scale).  Rows of the side buffer that have no children -- connection rows, aux nodes outside the crop, the
+    parents of a level that runs node by node -- have scale 0 and are exactly zero."""
+    k64, k_scale = EV.kidsum(topo, r64["out"], B, out_scale=torch.full_like(r64["out"], float(r64["out"].abs().max())))
+    k32 = EV.kidsum(topo, r32["out"], B, F32)[0]
+    assert ka.shape == k64.shape
+    rep.check("child sums" + tag, ka, k64, k32, k_scale)
+    own64, own_scale = EV.kidsum(topo, out, B)
+    own32 = EV.kidsum(topo, out, B, F32)[0]
+    rep.check("child sums of its own out" + tag, ka, own64, own32, own_scale)
+    never = (k_scale == 0).all(1)
+    assert not never.any() or float(ka.cpu()[never].abs().max()) == 0.0
+
+
 @pytest.mark.parametrize("case", T.LAYER_CASES, ids=str)
 def test_train_layer_against_fp64(case, capsys):
     """relu x residual x p in {0, 0.5} on one handle (residual on / off: the producer / consumer and the symmetric dX kernel), every
-    need_dx / need_dw form, equal bits on a second call, and once over child sums left by a previous launch."""
+    need_dx / need_dw form, equal bits on a second call, the child sums every form leaves behind, and once over child sums left by
+    a previous launch.  On 'grid-diagonal' handles the train forward and the residual dX are launches of the producer / consumer
+    kernel (its {mode 1 / 2, diag} forms), counted on the handle."""
     T.assert_input_condition(T.layer_condition(case))           # on the reference alone, before a kernel is looked at
     g, B = _graph(case)
     E = T.layer_edges(case)[0]
@@ -96,6 +119,8 @@ def test_train_layer_against_fp64(case, capsys):
     D = _dev(I)
     rep = CR.Report()
     chained_from = None
+    topo = EV.topology(*case[1:-1]) if g.kidsum_rows > 0 else None
+    ps = case[0] == "diag" and ops.lower_sums_supported(g.bwd)          # (EG_TRAIN_PS=0: the symmetric kernel throughout)
     for relu, residual, p in itertools.product((False, True), (False, True), (0.0, 0.5)):
         ref = lambda dt, x=I["x"], relu=relu, residual=residual, p=p: T.layer64(
             E, B, x, I["weight"], I["bias"], I["gamma"], I["beta"], I["rmean"], I["rvar"], relu=relu, p=p, seed=T.SEED_L,
@@ -107,7 +132,9 @@ def test_train_layer_against_fp64(case, capsys):
             rm, rv = D["rmean"].clone(), D["rvar"].clone()
             return ops.gcn_layer_train_fwd(g, B, x, D["weight"], D["bias"], D["gamma"], D["beta"], rm, rv, T.MOMENTUM, T.EPS, relu, p,
                                            T.SEED_L, residual, **kw), rm, rv
+        launches = g.ps_launches
         got, rm, rv = fwd()
+        assert not ps or g.ps_launches == launches + 1
         _check_layer_forward(rep, tag, got, rm, rv, r64, r32)
         again, rm2, rv2 = fwd()
         assert all(torch.equal(a, b) for a, b in zip(got + (rm, rv), again + (rm2, rv2)))
@@ -116,16 +143,20 @@ def test_train_layer_against_fp64(case, capsys):
         for need_dx, need_dw in ((True, True), (True, False), (False, True)):
             bwd = lambda: ops.gcn_layer_bwd(g.bwd, B, D["dy"], z, agg, D["weight"], D["gamma"], D["beta"], bn, relu, p, T.SEED_L, residual,
                                             need_dx, need_dw)
+            launches = g.ps_launches
             res = bwd()
+            assert not ps or g.ps_launches == launches + (1 if need_dx and residual else 0)
             _check_layer_backward(rep, tag, res, r64, r32, need_dx, need_dw)
             if first is None:
                 first = res
                 assert all(torch.equal(a, b) for a, b in zip(res, bwd()))
-        if g.kidsum_rows > 0 and relu and residual and p > 0:
-            # the same launch leaving the child sums of its output behind: the same out under the same bounds ...
+        if g.kidsum_rows > 0:
+            # the same launch leaving the child sums of its output behind: the same out under the same bounds, and the sums ...
             ka = ops.new_kidsum(g, B)
             got_k, rm, rv = fwd(kidsum_out=ka)
             _check_layer_forward(rep, tag, got_k, rm, rv, r64, r32)
+            _check_child_sums(rep, tag, topo, B, ka, got_k[0], r64, r32)
+        if g.kidsum_rows > 0 and relu and residual and p > 0:
             chained_from = (got_k[0], ka)
     if chained_from is not None:
         # ... and a layer on top of it that reads one child-sum row in place of four child rows (no ReLU: no kink, whatever its input)
@@ -133,8 +164,10 @@ def test_train_layer_against_fp64(case, capsys):
         r64, r32 = _both(lambda dt: T.layer64(E, B, x2.cpu(), I["weight"], I["bias"], I["gamma"], I["beta"], I["rmean"], I["rvar"], relu=False,
                                               p=0.5, seed=T.SEED_L + 1, residual=True, dy=I["dy"], dtype=dt))
         rm, rv = D["rmean"].clone(), D["rvar"].clone()
+        launches = g.ps_launches
         got = ops.gcn_layer_train_fwd(g, B, x2, D["weight"], D["bias"], D["gamma"], D["beta"], rm, rv, T.MOMENTUM, T.EPS, False, 0.5,
                                       T.SEED_L + 1, True, kidsum_in=ka)
+        assert not ps or g.ps_launches == launches + 1
         _check_layer_forward(rep, " over child sums", got, rm, rv, r64, r32)
         out, z, agg, bn = got
         res = ops.gcn_layer_bwd(g.bwd, B, D["dy"], z, agg, D["weight"], D["gamma"], D["beta"], bn, False, 0.5, T.SEED_L + 1, True, True, True)
@@ -310,39 +343,52 @@ def test_no_layer_sums_from_the_heads_backward_below_one_tile():
     assert torch.equal(dh, dh0) and torch.equal(grads, grads0)
 
 
-@pytest.mark.parametrize("frame,naux,B,small", [(16, 3, 2, True), (224, 7, 4, False)])
-def test_layer_sums_handed_down_by_the_dx_launch_against_fp64(frame, naux, B, small, capsys):
+@pytest.mark.parametrize("handle,B,cut", T.LOWER_SUMS_CASES, ids=str)
+def test_layer_sums_handed_down_by_the_dx_launch_against_fp64(handle, B, cut, capsys):
     """`lsums` of gcn_layer_bwd(lower=) against layer_sums64 on the kernel's own dx, on both sides of TILE_SUMS_SMALL (train.hip: one
-    launch up to 4096 tiles, two stages above); at the small size also fed back into the lower layer's backward."""
-    g = ops.Graph.topo(frame, naux)
+    launch up to 4096 tiles, two stages above), on handles with coordinate rows, connection nodes (their rows are rows of the frame
+    like any other: inside [0, row_hi)) and 'grid-diagonal' levels (the {mode 3, diag} form), over all rows of a frame and with the
+    last four left out, for a lower layer with ReLU and dropout, with neither, and with ReLU alone; at the small sizes also fed back
+    into the lower layer's backward."""
+    frame, naux, main_only, coord, conn, dm, da = handle
+    g = ops.Graph.topo(frame, naux, main_only, coord, use_connection_nodes=conn, diag_main=dm, diag_aux=da)
     if not ops.lower_sums_supported(g.bwd):
         pytest.skip("EG_TRAIN_PS=0: the dX launch is the symmetric kernel's, which hands no sums down")
     n = g.num_nodes
-    assert (g.num_tiles * B <= 4096) == small
-    rows, row_hi = B * n, n - 4
+    small = g.num_tiles * B <= 4096
+    assert small == (frame != 224) and g.hybrid == (dm or da or conn)
+    rows = B * n
+    E = T.topo_edges(*handle)
+    assert E[0] == n
     up, low = _kept_layer(rows, seed=frame), _kept_layer(rows, seed=frame + 1)
     dy = torch.from_numpy(np.random.default_rng(frame + 2).standard_normal((rows, C), dtype=np.float32)).to(DEV)
-    relu_l, p_l, seed_l = True, 0.5, T.SEED_L + 7
-    z_low = low["z"].to(DEV)
-    res = ops.gcn_layer_bwd(g.bwd, B, dy, up["z"].to(DEV), up["agg"].to(DEV), up["weight"].to(DEV), up["gamma"].to(DEV), up["beta"].to(DEV),
-                            up["bn"], True, 0.5, T.SEED_L, True, True, True, lower=(z_low, low["bn"], relu_l, p_l, seed_l, row_hi))
-    dx, lsums = res[0], res[5]
-    plain = ops.gcn_layer_bwd(g.bwd, B, dy, up["z"].to(DEV), up["agg"].to(DEV), up["weight"].to(DEV), up["gamma"].to(DEV), up["beta"].to(DEV),
-                              up["bn"], True, 0.5, T.SEED_L, True, True, True)
-    assert all(torch.equal(a, b) for a, b in zip(res[:5], plain))           # the by-product changes nothing else
-    mask = CR.hash_mask(rows, C, p_l, seed_l)
-    sel = T.frame_rows(B, n, 0, row_hi)
-    dxc, bn = dx.cpu(), low["bn"].cpu()
-    s64, s32 = _both(lambda dt: T.layer_sums64(dxc, low["z"], bn, None, None, relu_l, mask, sel, dtype=dt))
-    scale = T.layer_sums64(dxc.abs(), low["z"], bn, None, None, relu_l, mask, sel, absolute=True)
+    seed_l = T.SEED_L + 7
+    z_low, bn = low["z"].to(DEV), low["bn"].cpu()
+    upper = lambda **kw: ops.gcn_layer_bwd(g.bwd, B, dy, up["z"].to(DEV), up["agg"].to(DEV), up["weight"].to(DEV), up["gamma"].to(DEV),
+                                           up["beta"].to(DEV), up["bn"], True, 0.5, T.SEED_L, True, True, True, **kw)
+    launches = g.ps_launches
+    plain = upper()
+    assert g.ps_launches == launches + 1                        # the dX launch is the producer / consumer kernel's
+    dxc = plain[0].cpu()
     rep = CR.Report()
-    assert lsums.dtype == F64 and lsums.numel() == 2 * C
-    rep.check("sum g", lsums[:C], s64[:C], s32[:C], scale[:C])
-    rep.check("sum g xhat", lsums[C:], s64[C:], s32[C:], scale[C:])
-    if small:
-        E = T.topo_edges(frame, naux)
-        _check_fed_back(rep, " given the dX launch's sums", E, B, g, dx, low, relu_l, p_l, seed_l, (lsums, B, 0, row_hi), mask)
-    _finish(rep, f"layer sums from the dX launch, frame {frame} aux {naux} B {B}: {g.num_tiles * B} tiles", capsys)
+    for row_hi, (relu_l, p_l) in itertools.product(cut, ((True, 0.5), (False, 0.0), (True, 0.0))):
+        tag = f" row_hi {'n' if row_hi == 0 else f'n - {-row_hi}'} relu {int(relu_l)} p {p_l:g}"
+        row_hi += n
+        launches = g.ps_launches
+        res = upper(lower=(z_low, low["bn"], relu_l, p_l, seed_l, row_hi))
+        assert g.ps_launches == launches + 1
+        dx, lsums = res[0], res[5]
+        assert all(torch.equal(a, b) for a, b in zip(res[:5], plain))       # the by-product changes nothing else
+        mask = CR.hash_mask(rows, C, p_l, seed_l) if p_l > 0 else None
+        sel = T.frame_rows(B, n, 0, row_hi)
+        s64, s32 = _both(lambda dt: T.layer_sums64(dxc, low["z"], bn, None, None, relu_l, mask, sel, dtype=dt))
+        scale = T.layer_sums64(dxc.abs(), low["z"], bn, None, None, relu_l, mask, sel, absolute=True)
+        assert lsums.dtype == F64 and lsums.numel() == 2 * C
+        rep.check("sum g" + tag, lsums[:C], s64[:C], s32[:C], scale[:C])
+        rep.check("sum g xhat" + tag, lsums[C:], s64[C:], s32[C:], scale[C:])
+        if small:
+            _check_fed_back(rep, " given the dX launch's sums," + tag, E, B, g, dx, low, relu_l, p_l, seed_l, (lsums, B, 0, row_hi), mask)
+    _finish(rep, f"layer sums from the dX launch, handle {handle} B {B}: {g.num_tiles * B} tiles", capsys)
 
 
 # ---------------------------------------------------------------------------

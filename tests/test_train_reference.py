@@ -17,6 +17,15 @@ C = 128
 F64, F32 = torch.float64, torch.float32
 
 
+def _case(handle, B):
+    """The layer case of a TOPO_HANDLES (5 flags) or DIAG_TRAIN_HANDLES (7) entry."""
+    return (("diag",) if len(handle) == 7 else ("topo",)) + handle + (B,)
+
+
+def _topology(handle):
+    return HierTopology(TopologySpec(*handle[:5], *T.graph_types(*handle[5:])))
+
+
 def _close(a, b, rel=1e-12):
     err = float((a.to(F64) - b.to(F64)).abs().max())
     return err <= rel * max(float(b.abs().max()), 1e-300)
@@ -26,12 +35,13 @@ def _close(a, b, rel=1e-12):
 # the reference against the oracle's own modules, float64, train mode, p = 0
 # ---------------------------------------------------------------------------
 @pytest.mark.parametrize("relu", [False, True])
-@pytest.mark.parametrize("handle,B", [((8, 1, False, False, False), 3), ((17, 3, False, True, False), 2), ((16, 3, False, False, True), 1)])
+@pytest.mark.parametrize("handle,B", [((8, 1, False, False, False), 3), ((17, 3, False, True, False), 2), ((16, 3, False, False, True), 1),
+                                      ((16, 3, False, False, True, True, True), 2)])           # 'grid-diagonal' levels + connection nodes
 def test_layer64_equals_the_oracle_layer_in_float64(handle, B, relu):
-    case = ("topo",) + handle + (B,)
+    case = _case(handle, B)
     E, B, rows = T.layer_edges(case)
     I = T.layer_inputs(case, seed=7)
-    topo = HierTopology(TopologySpec(*handle))
+    topo = _topology(handle)                                     # (the oracle sees nothing of it but the edge_index)
     ei = torch.from_numpy(topo.batched_edge_index(B).astype(np.int64))
     conv, bn = O.OracleGCNConv(C, C), torch.nn.BatchNorm1d(C, eps=T.EPS, momentum=T.MOMENTUM)
     layer = O.OracleSequential("x, edge_index", [(conv, "x, edge_index -> x"), bn, torch.nn.Dropout(p=0.0),
@@ -106,11 +116,11 @@ def test_directed_ahat_equals_the_dense_construction():
     assert _close(T.ahat(E, x, 1), A @ x) and _close(T.ahat_t(E, x, 1), A.t() @ x)
 
 
-@pytest.mark.parametrize("handle", T.TOPO_HANDLES)
+@pytest.mark.parametrize("handle", T.TOPO_HANDLES + T.DIAG_TRAIN_HANDLES)
 def test_topology_ahat_equals_the_oracles_normalisation(handle):
-    topo = HierTopology(TopologySpec(*handle))
+    topo = _topology(handle)
     ei = torch.from_numpy(topo.batched_edge_index(2).astype(np.int64))
-    x = T.layer_inputs(("topo",) + handle + (2,), seed=1)["x"].double()
+    x = T.layer_inputs(_case(handle, 2), seed=1)["x"].double()
     assert _close(T.ahat(T.topo_edges(*handle), x, 2), O.gcn_conv_dense64(x, ei, torch.eye(C, dtype=F64), None))
     # the batched edge list as one graph: the same operator
     E1 = T.edges_of(topo.batched_edge_index(2), 2 * topo.num_nodes)
@@ -152,7 +162,9 @@ def _bounded(ref, names):
 
 @pytest.mark.parametrize("case", T.LAYER_CASES, ids=str)
 def test_layer_cases_meet_the_input_condition_and_scales_bound_their_quantities(case):
-    assert T.LAYER_B == {}                                       # no case had to give up frames
+    # no case had to give up frames but the two frame-30 'grid-diagonal' handles at B = 3 (train_reference.LAYER_SEED: 2 frames)
+    assert set(T.LAYER_B) == {c for c in T.DIAG_CASES if c[1] == 30 and c[-1] == 3} and set(T.LAYER_B.values()) == {2}
+    assert T.layer_edges(case)[1] == T.LAYER_B.get(case, case[-1] if case[0] in ("topo", "diag") else 1)
     cond = T.assert_input_condition(T.layer_condition(case))
     print(f"\n  {case}: smallest |BN output| {cond[0]:.3e}  margin {cond[1]:.3e}  active {cond[2]}  kept {cond[3]}")
     E, B, rows = T.layer_edges(case)
@@ -181,8 +193,8 @@ def test_heads_cases_meet_the_input_condition_and_scales_bound_their_quantities(
 
 def test_seed_search_finds_the_committed_seeds():
     """The tables are what the search gives (one small case each: the whole search is minutes)."""
-    case = ("topo", 8, 1, False, False, False, 3)
-    assert T.search_seed(T.layer_condition, case, 1000) == T.LAYER_SEED[case]
+    for case in (("topo", 8, 1, False, False, False, 3), ("diag", 16, 3, False, False, True, True, True, 1)):
+        assert T.search_seed(T.layer_condition, case, 1000) == T.LAYER_SEED[case]
     assert T.search_seed(T.heads_condition, T.HEADS_CASES[1], 2000) == T.HEADS_SEED[T.HEADS_CASES[1][:4]]
 
 
@@ -241,6 +253,50 @@ def test_the_rule_passes_float32_and_fails_planted_errors_in_the_layer():
     t = r32["out"].clone()
     t[rows - 1] = t[rows - 2]
     assert _fails("out", t, r64, r32, big("out"))
+
+
+DIAG_MUTATION_CASE = ("diag", 17, 3, False, True, False, True, True, 3)        # ragged patches, both grids 'grid-diagonal'
+
+
+def test_the_rule_tells_a_wrong_diagonal_stencil_from_rounding():
+    """On a 'grid-diagonal' case's inputs: the float32 reference passes; a reference on the same handle's 4-neighbour edges (every
+    diagonal tap missing, the degrees those of the 4-neighbour graph) and one with the edges of ONE diagonal direction removed (the
+    degrees as they are: a kernel that skips a tap) fail agg, z, dx and dw -- before a kernel is looked at."""
+    case = DIAG_MUTATION_CASE
+    E, B, rows = T.layer_edges(case)
+    I = T.layer_inputs(case)
+    T.assert_input_condition(T.layer_condition(case))
+    kw = dict(relu=True, p=0.5, seed=T.SEED_L, residual=True, dy=I["dy"])
+    layer = lambda edges, dt: T.layer64(edges, B, I["x"], I["weight"], I["bias"], I["gamma"], I["beta"], I["rmean"], I["rvar"], **kw, dtype=dt)
+    r64, r32 = layer(E, F64), layer(E, F32)
+    names = ("agg", "z", "dx", "dw")
+    for k in names + ("mean", "var", "running_mean", "running_var", "dgamma", "dbeta"):
+        assert not _fails(k, r32[k], r64, r32), k
+    # 1. the 4-neighbour stencil on every level
+    E4 = T.topo_edges(*case[1:6])
+    assert E4[0] == E[0] and E4[1].numel() < E[1].numel()
+    m = layer(E4, F32)
+    for k in names:
+        assert _fails(k, m[k], r64, r32), k
+    # 2. one diagonal direction missing (down-right in the row-major order of a level: target = source + side + 1), forward and back
+    topo = _topology(case[1:-1])
+    n, src, dst, w_edge, w_self = E
+    drop = torch.zeros(src.numel(), dtype=torch.bool)
+    for lv in list(topo.aux_levels) + [topo.main]:
+        inside = (src >= lv.base) & (src < lv.base + lv.size) & (dst >= lv.base) & (dst < lv.base + lv.size)
+        drop |= inside & ((dst - src).abs() == lv.side + 1)
+    assert 0 < int(drop.sum()) < int((src.numel() - E4[1].numel()) * 0.6)           # about half of the diagonal edges
+    keep = ~drop
+    m = layer((n, src[keep], dst[keep], w_edge[keep], w_self), F32)
+    for k in names:
+        assert _fails(k, m[k], r64, r32), k
+    # ... on one level alone: the 2 x 2 or 4 x 4 levels at the head of the frame hold few edges, the error is not diluted
+    lv = topo.aux_levels[0]
+    one = drop & (src < lv.base + lv.size) & (dst < lv.base + lv.size)
+    assert 0 < int(one.sum()) <= 2 * (lv.side - 1) ** 2
+    m = layer((n, src[~one], dst[~one], w_edge[~one], w_self), F32)
+    for k in names:
+        assert _fails(k, m[k], r64, r32), k
 
 
 def test_the_rule_passes_float32_and_fails_planted_errors_in_the_heads():

@@ -41,10 +41,16 @@ def edges_of(edge_index, n: int):
     return n, e[0], e[1], dis[e[0]] * dis[e[1]], dis * dis
 
 
+def graph_types(diag_main=False, diag_aux=False):
+    """(main_graph_type, aux_graph_type) of a TopologySpec: 'grid-diagonal' levels have 8 neighbours, 'grid' levels 4."""
+    return ("grid-diagonal" if diag_main else "grid"), ("grid-diagonal" if diag_aux else "grid")
+
+
 @functools.lru_cache(maxsize=None)
-def topo_edges(frame, naux, main_only=False, coord=False, conn=False):
-    """edges_of one frame of the (frame, naux, main_only, coord, conn) topology."""
-    topo = HierTopology(TopologySpec(frame, naux, main_only, coord, conn))
+def topo_edges(frame, naux, main_only=False, coord=False, conn=False, diag_main=False, diag_aux=False):
+    """edges_of one frame of the (frame, naux, main_only, coord, conn, diag_main, diag_aux) topology (eval_reference.topo_edges is
+    this function)."""
+    topo = HierTopology(TopologySpec(frame, naux, main_only, coord, conn, *graph_types(diag_main, diag_aux)))
     return edges_of(topo.edge_index(), topo.num_nodes)
 
 
@@ -326,6 +332,19 @@ TOPO_HANDLES = [(8, 1, False, False, False),        # 68 nodes: a 4-row last til
                 (16, 3, False, True, False),        # coordinate nodes
                 (16, 3, False, False, True)]        # connection nodes
 LAYER_CASES = [("topo",) + h + (B,) for h in TOPO_HANDLES for B in (1, 3)] + [("directed", 300, 1500, 1), ("batched", 16, 3, 2)]
+# "diag": (frame, naux, main_only, coord, conn, diag_main, diag_aux) -- handles with 'grid-diagonal' (8-neighbour) levels, whose
+# train forward and residual dX run as the {mode 1 / 2 / 3, diag} forms of the producer / consumer kernel (ps_form.h), the
+# activation pass with child sums in tile order (bn_act_tiles.hip), the connection-node pre-pass (conn.hip) and, residual off, the
+# symmetric kernel on the handle's one-frame CSR
+DIAG_TRAIN_HANDLES = [(16, 3, False, False, False, True, True),        # both grids diagonal
+                      (17, 3, False, True, False, True, True),         # ragged patches + coordinate nodes
+                      (30, 3, False, False, False, False, True),       # aux levels only; sides that do not divide the frame
+                      (16, 2, True, False, False, True, False),        # main grid only: no child sums
+                      (8, 2, False, False, False, True, True),         # levels below 8 columns: node by node, parents never written
+                      (16, 3, False, False, True, True, True),         # connection nodes on diagonal levels
+                      (30, 3, False, True, True, True, False)]         # connection + coordinate nodes, diagonal main grid
+DIAG_CASES = [("diag",) + h + (B,) for h in DIAG_TRAIN_HANDLES for B in (1, 3)]
+LAYER_CASES += DIAG_CASES
 # input seeds found on the CPU (search_seed: the first of at most 200 that meets the condition); a case it finds none for gets a smaller B
 LAYER_SEED = {("topo", 8, 1, False, False, False, 1): 1000, ("topo", 8, 1, False, False, False, 3): 1000,
               ("topo", 16, 3, False, False, False, 1): 1002, ("topo", 16, 3, False, False, False, 3): 1021,
@@ -334,14 +353,37 @@ LAYER_SEED = {("topo", 8, 1, False, False, False, 1): 1000, ("topo", 8, 1, False
               ("topo", 16, 3, False, True, False, 1): 1001, ("topo", 16, 3, False, True, False, 3): 1036,
               ("topo", 16, 3, False, False, True, 1): 1000, ("topo", 16, 3, False, False, True, 3): 1057,
               ("directed", 300, 1500, 1): 1000, ("batched", 16, 3, 2): 1015}
-LAYER_B = {}                                        # case -> the B it runs with where that is not the B it names
+# the "diag" cases: search_seed(layer_condition, case, 1000, tries=4000), the condition, the margin and the headroom as they are.  The
+# 200 seeds of the default search hold none for (17, 3, coordinate nodes) at B = 3 (1131 rows: 1371 is the first) and none for the two
+# frame-30 handles (984 / 992 nodes) at B = 3 or at B = 2.  Those two run at B = 2 (LAYER_B: about 252 000 BatchNorm outputs, of
+# which none may lie within 1.5 x 2.2e-5 of 0), where 1871 / 4377 are the first seeds with the search's headroom of 1.5
+LAYER_SEED.update({("diag", 16, 3, False, False, False, True, True, 1): 1004, ("diag", 16, 3, False, False, False, True, True, 3): 1077,
+                   ("diag", 17, 3, False, True, False, True, True, 1): 1000, ("diag", 17, 3, False, True, False, True, True, 3): 1371,
+                   ("diag", 30, 3, False, False, False, False, True, 1): 1006, ("diag", 30, 3, False, False, False, False, True, 3): 1871,
+                   ("diag", 16, 2, True, False, False, True, False, 1): 1001, ("diag", 16, 2, True, False, False, True, False, 3): 1034,
+                   ("diag", 8, 2, False, False, False, True, True, 1): 1000, ("diag", 8, 2, False, False, False, True, True, 3): 1000,
+                   ("diag", 16, 3, False, False, True, True, True, 1): 1008, ("diag", 16, 3, False, False, True, True, True, 3): 1023,
+                   ("diag", 30, 3, False, True, True, True, False, 1): 1020, ("diag", 30, 3, False, True, True, True, False, 3): 4377})
+# case -> the B it runs with where that is not the B it names
+LAYER_B = {("diag", 30, 3, False, False, False, False, True, 3): 2, ("diag", 30, 3, False, True, True, True, False, 3): 2}
+
+# -- the lower layer's sums out of the dX launch: ((frame, naux, main_only, coord, conn, diag_main, diag_aux), B, row_hi - n of every
+# run).  row_hi = n: every row of a frame; n - 4: without the last four (the coordinate rows, where a handle has them)
+LOWER_SUMS_CASES = [((16, 3, False, False, False, False, False), 2, (0, -4)),
+                    ((224, 7, False, False, False, False, False), 4, (-4,)),        # above TILE_SUMS_SMALL: the two-stage reduction
+                    ((16, 3, False, True, False, False, False), 2, (0, -4)),        # coordinate nodes
+                    ((16, 3, False, False, True, False, False), 2, (0,)),           # connection nodes
+                    ((16, 3, False, False, False, True, True), 2, (0,)),            # diagonal
+                    ((16, 3, False, False, True, True, True), 2, (0,)),             # diagonal + connection nodes
+                    ((8, 2, False, False, False, True, True), 2, (0,)),             # diagonal levels that run node by node
+                    ((30, 3, False, True, True, True, False), 2, (0, -4))]          # coordinate + connection nodes, diagonal main grid
 
 
 def layer_edges(case):
     """(E, frames the reference and the kernels walk, rows) of a layer case."""
     kind, B = case[0], LAYER_B.get(case, case[-1])
-    if kind == "topo":
-        E = topo_edges(*case[1:6])
+    if kind in ("topo", "diag"):
+        E = topo_edges(*case[1:-1])
         return E, B, B * E[0]
     if kind == "directed":
         n, m = case[1], case[2]
