@@ -20,8 +20,8 @@ HEADER_PATH = _PKG.parent / "include" / "echoglad_hip.h"
 
 EG_OK, EG_ERR_ARG, EG_ERR_UNSUPPORTED, EG_ERR_HIP = 0, -1, -2, -3
 # EG_ABI_VERSION of the include/echoglad_hip.h that the structures below and the wrappers' argument order were written for
-# (the header's version history says what each number added; 155: eg_sgd_step, eg_rmsprop_step)
-ABI_VERSION = 155
+# (the header's version history says what each number added; 155: eg_sgd_step, eg_rmsprop_step; 156: eg_heatmap_render)
+ABI_VERSION = 156
 
 _lib: Optional[ct.CDLL] = None
 
@@ -54,7 +54,7 @@ _SCALARS = {"int": ct.c_int, "int64_t": ct.c_int64, "uint64_t": ct.c_uint64, "fl
             "unsigned": ct.c_uint}
 _STRUCTS = {"eg_cls_train_params": ClsTrainParams, "eg_lower_sums": LowerSums, "eg_given_sums": GivenSums}
 # what a pointer that is passed as an address (c_void_p takes tensors' addresses, ctypes arrays and byref(...)) may point to
-_POINTEES = set(_SCALARS) | {"void", "char", "unsigned char", "double", "eg_graph", "eg_adam_tensor", "eg_sgd_tensor", "eg_rmsprop_tensor"}
+_POINTEES = set(_SCALARS) | {"void", "char", "unsigned char", "uint8_t", "double", "eg_graph", "eg_adam_tensor", "eg_sgd_tensor", "eg_rmsprop_tensor"}
 _DECLARATION = re.compile(r"([A-Za-z_][\w \t\n\*]*?)\b(eg_[a-z0-9_]+)\s*\(([^()]*)\)\s*;")
 
 

@@ -367,3 +367,20 @@ def update_evaluators(evaluators, preds, y, coord_preds, coord_y, pix2mm_x, pix2
             ev.update(coord_preds, coord_y, pix2mm_x, pix2mm_y, valid)
         else:
             ev.update(preds, y, pix2mm_x, pix2mm_y, valid)
+
+
+def prediction_table(evaluators, pix2mm_x, pix2mm_y):
+    """engine.py:602-639 (``create_prediction_df``) without pandas: a plain dict of lists, one entry per frame of the last update, in
+    the reference's column order -- ``pix2mm_x``, ``pix2mm_y``, the eight coordinate columns (``pred_ivs`` ... ``gt_lvpw``, an (h, w) pair
+    per frame) and the six width columns in mm -- from the landmark evaluator's ``get_predictions()`` (``pandas.DataFrame(table)``
+    gives the reference's frame).  pix2mm_x / pix2mm_y: tensors or sequences with one value per frame."""
+    def as_list(v):
+        return v.detach().reshape(-1).tolist() if isinstance(v, torch.Tensor) else [float(a) for a in v]
+    record = evaluators["landmarkcoorderror"].get_predictions()
+    if not record:
+        raise RuntimeError("prediction_table lists the predictions of the landmark evaluator's last update(): there is none")
+    table = {"pix2mm_x": as_list(pix2mm_x), "pix2mm_y": as_list(pix2mm_y)}
+    for group in ("coordinates", "widths"):
+        for key, value in record[group].items():
+            table[key] = value.tolist()
+    return table

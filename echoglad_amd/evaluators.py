@@ -208,6 +208,97 @@ class LandmarkExpectedCoordiantesEvaluator(object):
                        "gt_ivs": gt[:, 3], "gt_lvid_top": gt[:, 0], "gt_lvid_bot": gt[:, 1], "gt_lvpw": gt[:, 2]}
         return {"widths": widths, "coordinates": coordinates}
 
+    # ---- the heat-map figure (evaluators.py:485-616), both modes: rendered on the device by ops.heatmap_render -----------------------
+    def _logit_rows(self, t, name, frames=None):
+        """`t` as device float32 [frames * rows, 4] holding an F x F main grid per frame -> (rows, frames, the main grid's level)."""
+        F = self.frame_size
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} must be a CUDA (ROCm) tensor: the heat maps are rendered on the device, there is no CPU fallback")
+        if t.shape[-1] != 4:
+            raise ValueError(f"{name} must end in the 4 landmark channels, got {tuple(t.shape)}")
+        if frames is None:
+            frames = t.shape[0] if t.dim() == 3 else self.batch_size
+        rows = t.detach().reshape(-1, 4).to(torch.float32).contiguous()
+        if rows.shape[0] % frames or rows.shape[0] // frames < F * F:
+            raise ValueError(f"{rows.shape[0]} rows of {name} are not {frames} frames holding a {F} x {F} main grid each")
+        return rows, frames, (rows.shape[0] // frames - F * F, F)
+
+    def get_softmaxed_heatmap(self, y_pred):
+        """evaluators.py:485-495 on the device: y_pred [N, rows, 4] or [N * rows, 4] (then N is the evaluator's batch size), a CUDA
+        tensor -> the softmax over the main grid's rows as a CUDA float32 [N, F, F, 4] (eg_heatmap_render: exp(x - M) / S with the
+        decode kernel's (M, S); a channel without a finite logit is 0 everywhere).  Nothing is read back."""
+        rows, n, level = self._logit_rows(y_pred, "y_pred")
+        return ops.heatmap_render(rows, n, level, 0, n, want=("heat",))["heat"]
+
+    def get_overlays(self, x, landmark_preds, landmark_y, first=0, count=1):
+        """The overlay images of frames first .. first + count - 1 as CUDA uint8 [count, F, F, 3] (HWC, what ToPILImage yields):
+        {"pred_img": the frame under the per-channel normalised softmax heat maps, "gt_img": under the label heat maps, "coord_img":
+        the frame alone -- what the reference's overlay of an all-zero heat map is (evaluators.py:545)}.  x: CUDA [B, C, F, F], channel
+        0 is drawn (0.8 x grey); landmark_preds / landmark_y: the heat-map logits and labels [B * rows, 4] -- also with
+        use_coord_graph, where the coordinate predictions enter the figure only as markers.  One decode pass for (max, sum exp) and one
+        render launch (ops.heatmap_render), no host read-back and no matplotlib.
+        The reference's ``create_overlay_image(x, hms)`` on host tensors is not provided: it would be a torch fallback of this."""
+        B, F = self.batch_size, self.frame_size
+        lg, _, level = self._logit_rows(landmark_preds, "landmark_preds", B)
+        lb, _, _ = self._logit_rows(landmark_y, "landmark_y", B)
+        if lb.shape != lg.shape:
+            raise ValueError(f"landmark_y holds {lb.shape[0]} rows, landmark_preds {lg.shape[0]}")
+        if not x.is_cuda or x.dim() != 4 or x.shape[0] != B or tuple(x.shape[-2:]) != (F, F):
+            raise ValueError(f"x must be a CUDA tensor [{B}, C, {F}, {F}], got {tuple(x.shape)}")
+        r = ops.heatmap_render(lg, B, level, first, count, labels=lb, image=x.detach().to(torch.float32).contiguous(),
+                               want=("pred", "gt", "base"))
+        return {"pred_img": r["pred"], "gt_img": r["gt"], "coord_img": r["base"]}
+
+    def get_heatmaps(self, x, landmark_preds, landmark_y, coord_preds, pix2mm_x, pix2mm_y):
+        """evaluators.py:497-593: the figure of frame 0 of the batch of the last ``update`` -- one panel per group ("pred", "gt"; with
+        coord_preds "pred", "coord", "gt"): the overlay image, a white x per landmark, the IVS and LVPW segments in blue and the LVID
+        segment in red, the widths in mm as the panel's title, the width MAE / MPE of the frame as the figure's.  The images come from
+        ``get_overlays(count=1)`` (three 3 F^2-byte read-backs), the numbers from ``get_predictions()``; matplotlib draws on the host."""
+        try:
+            import matplotlib
+            matplotlib.use("Agg")
+            import matplotlib.pyplot as plt
+        except ImportError as e:
+            raise ImportError("LandmarkExpectedCoordiantesEvaluator.get_heatmaps draws its figure with matplotlib, which is not "
+                              "installed (get_overlays returns the images without it)") from e
+        record = self.get_predictions()
+        if not record:
+            raise RuntimeError("get_heatmaps shows the predictions of the last update(): there is none since the last reset()")
+        images = {k: v[0].cpu().numpy() for k, v in self.get_overlays(x, landmark_preds, landmark_y, 0, 1).items()}
+        widths = {k: v[0] for k, v in record["widths"].items()}
+        mae = self.calculate_width_MAE(widths)
+        mpe = self.calculate_width_MPE(widths)
+        points = {k: v[0].tolist() for k, v in record["coordinates"].items()}
+        groups = ("pred", "gt")
+        if coord_preds is not None:
+            c = coord_preds.detach().reshape(self.batch_size, -1, 2)[0].to(torch.float32).cpu()
+            px, py = pix2mm_x.detach().reshape(-1)[0].cpu(), pix2mm_y.detach().reshape(-1)[0].cpu()
+            for k, name in enumerate(NAMES):
+                points["coord_" + name] = c[k].tolist()
+            # (the reference passes (h, w) here where calculate_widths passes (w, h): pix2mm_x scales the h difference -- kept)
+            for name, (i, j) in (("ivs", (3, 0)), ("lvid", (0, 1)), ("lvpw", (1, 2))):
+                widths[f"coord_{name}_mm"] = pixel_length(c[i, 0], c[i, 1], c[j, 0], c[j, 1], px, py)
+            groups = ("pred", "coord", "gt")
+        fig, axs = plt.subplots(1, len(groups), figsize=(4 * len(groups), 5))
+        for ax, g in zip(axs, groups):
+            ax.imshow(images[g + "_img"])
+            for name in NAMES:
+                ax.plot(points[f"{g}_{name}"][1], points[f"{g}_{name}"][0], marker="x", color="white", markersize=4)
+            for a, b, colour in (("ivs", "lvid_top", "dodgerblue"), ("lvid_bot", "lvpw", "dodgerblue"), ("lvid_top", "lvid_bot", "red")):
+                pa, pb = points[f"{g}_{a}"], points[f"{g}_{b}"]
+                ax.plot([pa[1], pb[1]], [pa[0], pb[0]], color=colour, linewidth=1.5)
+            ax.set_title(self.heatmap_panel_title(g, widths))
+        plt.setp(axs[1].get_yticklabels(), visible=False)
+        fig.tight_layout()
+        fig.suptitle("MAE [mm] | IVS: {:.1f} | LVID: {:.1f} | LVPW: {:.1f}\nMPE [%] | IVS: {:.1f} | LVID: {:.1f} | LVPW: {:.1f}"
+                     .format(*(float(v) for v in mae + mpe)))
+        return fig
+
+    @staticmethod
+    def heatmap_panel_title(group, widths):
+        """The title of one panel of get_heatmaps: the group's three widths in mm (evaluators.py:578-580)."""
+        return "{}: [{:.1f}, {:.1f}, {:.1f}]".format(group, *(float(widths[f"{group}_{k}_mm"]) for k in ("ivs", "lvid", "lvpw")))
+
     # ---- device mode --------------------------------------------------------------------------------------------------------------
     def _allocate(self, device):
         B, N = self.batch_size, self.max_updates

@@ -14,9 +14,9 @@ from .train import (CLS_GRADS_FLOATS, bn_act_bwd, bn_act_fwd, bn_act_fwd_tiles, 
                     classifier_train_fwd_act, colsum128, dweight128, gcn_layer_bwd, gcn_layer_train_fwd, lower_sums_supported)
 from .coord import (COORD_MLP_GRADS_FLOATS, bilinear4, bilinear4_bwd, bilinear4_fwd, coord_mlp_bwd, coord_mlp_fwd,     # noqa: F401
                     coord_update_bwd, coord_update_fwd, scatter_coord_rows)
-from .criteria import (CONFUSION_MAX_CHANNELS, CONFUSION_WORKSPACE_BYTES, LANDMARK_DETAIL_FLOATS, LANDMARK_RECORD_FLOATS,   # noqa: F401
-                       bce_logits, bce_logits_fwd, bce_probs, bce_probs_fwd, confusion_counts, elm_reduce, heatmap_expect,
-                       heatmap_expect_bwd, heatmap_expect_fwd, landmark_criteria, landmark_record_coord, landmark_record_hm,
+from .criteria import (CONFUSION_MAX_CHANNELS, CONFUSION_WORKSPACE_BYTES, HEATMAP_RENDER_OUTPUTS, LANDMARK_DETAIL_FLOATS,   # noqa: F401
+                       LANDMARK_RECORD_FLOATS, bce_logits, bce_logits_fwd, bce_probs, bce_probs_fwd, confusion_counts, elm_reduce,
+                       heatmap_expect, heatmap_expect_bwd, heatmap_expect_fwd, heatmap_render, landmark_criteria, landmark_record_coord, landmark_record_hm,
                        landmark_record_workspace_bytes)
 from .frontend import adaptive_max_pool, adaptive_max_pool_train, conv3x3_relu_bn, conv3x3_relu_bn_train               # noqa: F401
 from .embedder import embed_block, embed_block_train, pyramid_block, pyramid_block_train                                        # noqa: F401

@@ -64,6 +64,59 @@ def heatmap_expect(logits, batch: int, levels, labels=None, valid=None):
     return _HeatmapExpectFn.apply(logits, batch, tuple(levels), labels, valid)
 
 
+HEATMAP_RENDER_OUTPUTS = ("heat", "pred", "gt", "base")
+
+
+def heatmap_render(logits: torch.Tensor, batch: int, level, first: int = 0, count: int = 1, labels: Optional[torch.Tensor] = None,
+                   image: Optional[torch.Tensor] = None, want=HEATMAP_RENDER_OUTPUTS):
+    """The pictures of one level (first row inside a frame's rows, side) of frames first .. first + count - 1 (eg_heatmap_render):
+    dict of device tensors, one per name in `want`:
+      "heat" float32 [count, side, side, 4]: softmax over the level's rows, exp(x - M) / S;
+      "pred" / "gt" / "base" uint8 [count, side, side, 3] (HWC): the frame (0.8 * image, black without one) under the per-channel
+      normalised heat maps exp(x - M) / under the labels / alone, in the reference's colours and operation order
+      (create_overlay_image + ToPILImage, evaluators.py:595-616), saturating at 255 where the reference's .byte() would wrap.
+    logits (and labels: "gt" needs them) float32 [batch * n_rows, 4]; image float32 [batch, C, side, side] (channel 0 is drawn).
+    The frames' rows are sliced, not copied; eg_heatmap_expect_fwd on that slice gives the level's
+    (M, S), then ONE launch renders: nothing is read back."""
+    if logits.shape[0] % batch:
+        raise RuntimeError("logit rows are not a multiple of the batch size")
+    n_rows = logits.shape[0] // batch
+    _check_rows(logits, "logits", None, 4)
+    _check_rows(labels, "labels", logits.shape[0], 4, optional=True)
+    start, side = int(level[0]), int(level[1])
+    first, count = int(first), int(count)
+    want = tuple(want)
+    if not want or any(w not in HEATMAP_RENDER_OUTPUTS for w in want):
+        raise RuntimeError(f"want must name at least one of {HEATMAP_RENDER_OUTPUTS}, got {want}")
+    if "gt" in want and labels is None:
+        raise RuntimeError('the "gt" image needs labels')
+    if count < 1 or first < 0 or first + count > batch:
+        raise RuntimeError(f"frames {first} .. {first + count - 1} are not inside a batch of {batch}")
+    if side < 1 or start < 0 or start + side * side > n_rows:
+        raise RuntimeError(f"level (start {start}, side {side}) is outside the frame's {n_rows} rows")
+    dev = logits.device
+    stride = 0
+    if image is not None:
+        if image.dim() != 4 or image.shape[0] != batch or tuple(image.shape[-2:]) != (side, side):
+            raise RuntimeError(f"image must be [{batch}, C, {side}, {side}], got {tuple(image.shape)}")
+        _check(image, "image", device=dev)
+        stride = image.numel() // batch
+        image = image[first:first + count]                    # (a view: channel 0 of frame i starts at i * stride)
+    lg = logits[first * n_rows:(first + count) * n_rows]
+    lb = None if labels is None else labels[first * n_rows:(first + count) * n_rows]
+    lg, lb = _aligned16(lg, lb)
+    stats = heatmap_expect_fwd(lg, count, [(start, side)])["stats"]
+    out = {}
+    if "heat" in want:
+        out["heat"] = torch.empty(count, side, side, 4, dtype=torch.float32, device=dev)
+    for name in ("pred", "gt", "base"):
+        if name in want:
+            out[name] = torch.empty(count, side, side, 3, dtype=torch.uint8, device=dev)
+    call("eg_heatmap_render", lg, lb if "gt" in want else None, image, stride, stats, count, n_rows, start, side,
+         out.get("heat"), out.get("pred"), out.get("gt"), out.get("base"))
+    return out
+
+
 def elm_reduce(expect, gt, vmean, inv_side, weight: float):
     """ExpectedLandmarkMSE's combination of the per-(frame, level, channel) expectations and its gradient in one launch
     (eg_elm_reduce) -> (loss [1], d loss / d expect [B, L, 4, 2])."""

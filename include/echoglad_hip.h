@@ -103,8 +103,9 @@ extern "C" {
  * eg_pyramid_conv_bwd_weight.  152: eg_gcn_layer_cls_fold_split_fwd.
  * 153: eg_conv1x1_relu_pack_bwd_workspace_bytes, eg_conv1x1_relu_pack_bwd_plan, eg_conv1x1_relu_pack_bwd.
  * 154: eg_conv1x1_relu_heads_fwd.
- * 155: eg_sgd_step, eg_rmsprop_step. */
-#define EG_ABI_VERSION 155
+ * 155: eg_sgd_step, eg_rmsprop_step.
+ * 156: eg_heatmap_render. */
+#define EG_ABI_VERSION 156
 
 #define EG_CHANNELS 128 /* node_embedding_dim == node_hidden_dim (configs/default.yml:13-14) */
 
@@ -629,6 +630,32 @@ int eg_heatmap_expect_fwd(const float* logits, const float* labels, const float*
 int eg_heatmap_expect_bwd(const float* logits, const float* expect, const float* stats, const float* d_expect, int batch,
                           int64_t n_rows, const int* level_start, const int* level_side, int n_levels, float* d_logits,
                           eg_stream_t stream);
+/* eg_heatmap_render: the pictures of one level of `count` consecutive frames in ONE launch (src/core/evaluators.py:485-616:
+ * get_softmaxed_heatmap, the per-channel normalisation of get_heatmaps, create_overlay_image + ToPILImage).  No workspace, no
+ * atomics, no read-back.  The level is rows level_start .. level_start + side * side - 1 of every frame, row-major (h, w); the
+ * main grid is level_start = n_rows - F * F, side = F.
+ *   logits [count * n_rows, 4] f32 (16-byte aligned); labels the same, or NULL; stats [count,4,2] f32 = (M, S) per frame and
+ *   channel: what eg_heatmap_expect_fwd writes as `stats` for that ONE level.
+ *   image: pixel (h, w) of frame i is image[i * image_stride + h * side + w] (channel 0 of a contiguous [B,C,F,F] tensor:
+ *   image_stride = C * F * F, no copy); NULL: black.
+ *   heat [count,side,side,4] f32 (16-byte aligned) = expf(x - M) / S, the p of eg_heatmap_expect_bwd; x = -inf gives 0, a channel
+ *   whose M is -inf (no finite logit) is 0 everywhere.
+ *   pred_rgb / gt_rgb / base_rgb [count,side,side,3] u8 (HWC: what ToPILImage yields).  In fp32, in the reference's operation
+ *   order (colour * value, then max, then * 255, then truncate):
+ *     e_c = expf(x_c - M_c)      the per-channel normalised map: the reference forms p / max p and max p is 1 / S -- the value
+ *                                that quotient rounds to, without a second reduction
+ *     base = max(0, 0.8f * image)                                (the same for R, G and B)
+ *     pred_k = max(base, max_c col[c][k] * e_c),  gt_k = max(base, max_c col[c][k] * label_c)
+ *     col = (0,1,1), (1,0.7,0.9), (0,1,0), (1,0,0) for channels 0..3
+ *     byte = (uint8) min(v * 255.0f, 255.0f), truncated toward zero; NaN gives 0.
+ *   The reference's .byte() wraps past 255 (or is undefined there); this SATURATES at 255 -- a difference that cannot arise
+ *   for frames in [0, 1], where no value exceeds 1.
+ * Every output may be NULL, at least one must be given; gt_rgb needs labels.  EG_ERR_ARG (nothing launched): NULL logits or
+ * stats, no output, gt_rgb without labels, misaligned logits / labels / heat, count < 1, side < 1, level_start < 0,
+ * level_start + side * side > n_rows. */
+int eg_heatmap_render(const float* logits, const float* labels, const float* image, int64_t image_stride,
+                      const float* stats, int count, int64_t n_rows, int level_start, int side,
+                      float* heat, uint8_t* pred_rgb, uint8_t* gt_rgb, uint8_t* base_rgb, eg_stream_t stream);
 /* ExpectedLandmarkMSE's combination of those expectations (criterion.py:133-151) and its gradient in one launch:
  *   loss[0] = weight * sum_{l,c,xy} [ sum_b ((expect - gt) * inv_side[l])^2 * vmean ] / nv,  nv = sum_b vmean (1 where 0);
  *   d_expect [batch,n_levels,4,2] = d loss / d expect.  inv_side: DEVICE array [n_levels] = 1 / level side. */
