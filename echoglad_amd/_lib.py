@@ -20,8 +20,9 @@ HEADER_PATH = _PKG.parent / "include" / "echoglad_hip.h"
 
 EG_OK, EG_ERR_ARG, EG_ERR_UNSUPPORTED, EG_ERR_HIP = 0, -1, -2, -3
 # EG_ABI_VERSION of the include/echoglad_hip.h that the structures below and the wrappers' argument order were written for
-# (the header's version history says what each number added; 155: eg_sgd_step, eg_rmsprop_step; 156: eg_heatmap_render)
-ABI_VERSION = 156
+# (the header's version history says what each number added; 155: eg_sgd_step, eg_rmsprop_step; 156: eg_heatmap_render;
+# 157: eg_conn_rows_plan / _workspace_bytes / _fwd / _bwd)
+ABI_VERSION = 157
 
 _lib: Optional[ct.CDLL] = None
 

@@ -16,7 +16,7 @@ PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIBDIR = PKG / "lib"
 LIBNAME = "libechoglad_hip.so"
-SOURCES = ["graph.hip", "topo_tables.hip", "gcn_layer.hip", "gcn_layer_ps.hip", "gcn_layer_ps_split.hip", "gcn_layer_ps_fold_split.hip", "conn.hip", "classifier.hip", "tail_heads.hip", "train.hip", "bn_act_tiles.hip", "cls_train.hip", "coord.hip", "coord_mlp.hip", "heatmap.hip", "heatmap_render.hip", "pack.hip", "pack_train.hip", "pool.hip", "adam.hip", "optim.hip", "metrics.hip", "labels.hip", "frame_prep.hip", "frontend.hip", "frontend_train.hip", "embedder.hip", "pyramid_conv.hip", "pyramid_train.hip"]
+SOURCES = ["graph.hip", "topo_tables.hip", "gcn_layer.hip", "gcn_layer_ps.hip", "gcn_layer_ps_split.hip", "gcn_layer_ps_fold_split.hip", "conn.hip", "classifier.hip", "tail_heads.hip", "train.hip", "bn_act_tiles.hip", "cls_train.hip", "coord.hip", "coord_mlp.hip", "heatmap.hip", "heatmap_render.hip", "pack.hip", "pack_train.hip", "conn_rows.hip", "pool.hip", "adam.hip", "optim.hip", "metrics.hip", "labels.hip", "frame_prep.hip", "frontend.hip", "frontend_train.hip", "embedder.hip", "pyramid_conv.hip", "pyramid_train.hip"]
 ARCH = "gfx950"
 # per-file flags and extra dependencies, and objects whose device code must hold no packed fp32 vector instruction.
 # gcn_layer_ps_split.hip (the bf16-path instantiations of the layer kernel, gcn_layer_ps.hip included) is compiled without them:

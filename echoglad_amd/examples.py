@@ -90,12 +90,13 @@ class UNetNodeFeatureModel(HierarchicalPatchModel):
         ``train=True``: then training mode with autograd on takes ``nn.unet_decoder_maps_train`` (batch statistics, HIP backward,
         bit-reproducible); eval with gradients stays on torch.  ``tail=True``, independent of ``train``: whenever autograd is on,
         the tail (``linears`` + ReLU + packing) takes its fixed-order HIP backward (eg_conv1x1_relu_pack_bwd) instead of torch's
-        1 x 1 convolution gradients, the last piece of the step that was not reproducible bit for bit.  Not with
-        ``use_connection_nodes``: the connection-node means below still differentiate torch's 1 x 1 convolutions, so the step
-        would silently stay non-reproducible."""
-        if flag and tail and self.use_connection_nodes:
+        1 x 1 convolution gradients, the last piece of the step that was not reproducible bit for bit.  With
+        ``use_connection_nodes`` only behind ``enable_hip_conn_rows()``: the torch connection-node means below differentiate torch's
+        1 x 1 convolutions, so the step would silently stay non-reproducible."""
+        if flag and tail and self.use_connection_nodes and not self.hip_conn_rows:
             raise ValueError("enable_hip_frontend(tail=True) with use_connection_nodes=True: the connection-node means of "
-                             "create_node_pixels differentiate torch's 1 x 1 convolutions, the step would not be bit-reproducible")
+                             "create_node_pixels differentiate torch's 1 x 1 convolutions, the step would not be bit-reproducible "
+                             "(call enable_hip_conn_rows() first: the means then run in HIP, in a fixed order)")
         self.hip_frontend = bool(flag)
         self.hip_frontend_train = bool(flag) and bool(train)
         self.hip_tail = bool(flag) and bool(tail)
@@ -124,12 +125,13 @@ class UNetNodeFeatureModel(HierarchicalPatchModel):
         if self.use_main_graph_only:
             feats, lin = feats[-1:], lin[-1:]
         conn = None
-        if self.use_connection_nodes and not self.use_main_graph_only:
+        mode = self._conn_rows_mode("level")            # enable_hip_conn_rows: means over the packed rows, inside the packing node
+        if self.use_connection_nodes and not self.use_main_graph_only and not mode:
             # the connection nodes start from the mean of every level's ACTIVATED map (models.py:737-752): activated here, once
             # more, on the coarse maps only -- they are a few percent of the frame-sized one -- and on the frame-sized map's mean
             with torch.set_grad_enabled(torch.is_grad_enabled()):
                 conn = torch.stack([F.relu(m(f)).mean(dim=(2, 3)) for f, m in zip(feats, lin)], dim=1)        # [B, naux + 1, 128]
-        return self.pack_node_features_linear(feats, lin, B, node_coords, conn, backward="hip" if self.hip_tail else "torch")
+        return self.pack_node_features_linear(feats, lin, B, node_coords, conn, backward="hip" if self.hip_tail else "torch", **mode)
 
 
 class UNetNoGNN(UNetNodeFeatureModel):

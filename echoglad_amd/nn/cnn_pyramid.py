@@ -148,6 +148,7 @@ class CNNHierarchicalPatchModel(HierarchicalPatchModel):
         L = len(outs)
         maps = [outs[L - 1 - g] for g in range(self.num_aux_graphs)] + [echo_frames]
         conn = None
-        if self.use_connection_nodes:
+        mode = self._conn_rows_mode("level")
+        if self.use_connection_nodes and not mode:
             conn = torch.stack([m.mean(dim=(2, 3)) for m in maps], dim=1)                     # [B, naux + 1, 128]
-        return self.pack_node_features(maps, B, node_coords, conn)
+        return self.pack_node_features(maps, B, node_coords, conn, **mode)

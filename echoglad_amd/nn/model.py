@@ -95,6 +95,7 @@ class HierarchicalPatchModel(nn.Module):
         self._static_feats: Dict[tuple, torch.Tensor] = {}
         self.hip_graph_captures = 0
         self.use_hip_graph = False
+        self.hip_conn_rows = False          # a plain attribute: no parameter, no buffer, not in the state_dict (enable_hip_conn_rows)
         # eval path: layer i leaves the child sums of its output in a side buffer for layer i+1
         # (eg_gcn_layer_fwd_chain); False runs every layer on its own
         self.chain_layers = bool(ROUTES.chain_layers)
@@ -124,6 +125,24 @@ class HierarchicalPatchModel(nn.Module):
         self._hip_graphs.clear()
         self._static_feats.clear()
         return self
+
+    def enable_hip_conn_rows(self, flag: bool = True) -> "HierarchicalPatchModel":
+        """Opt in (models with ``use_connection_nodes``; without them the switch has no effect): the connection rows of the node
+        features are column means over the packed level rows themselves, taken in HIP inside the packing call's autograd node
+        (``conn_rows=`` of ops.pyramid_pack / pack_levels / conv1x1_relu_pack_levels: eg_conn_rows_fwd / _bwd, a fixed order of
+        summation both ways) -- no torch mean, no second pass over the level maps, no clone of the node array.  The values differ
+        from the torch route's by the order of an fp32 sum.  Off (the default): nothing changes.  ``enable_hip_conn_rows(False)``
+        while a UNet model's ``hip_tail`` is on is a ValueError: that tail is only reproducible with this switch.  Returns self."""
+        if not flag and getattr(self, "hip_tail", False) and self.use_connection_nodes:
+            raise ValueError("enable_hip_conn_rows(False) while enable_hip_frontend(tail=True) is on with use_connection_nodes=True: "
+                             "switch the tail off first (the torch means would make the step non-reproducible)")
+        self.hip_conn_rows = bool(flag)
+        return self
+
+    def _conn_rows_mode(self, mode: str) -> dict:
+        """{"conn_rows": mode} where this model's connection rows come from the packing call (enable_hip_conn_rows), else {}: the
+        keyword is passed on only with the switch on, every call with it off is the call it was."""
+        return {"conn_rows": mode} if (self.hip_conn_rows and self.use_connection_nodes and not self.use_main_graph_only) else {}
 
     def _static_node_feats(self, B: int, inputs) -> Optional[torch.Tensor]:
         """The static node-feature buffer ``forward()``'s packing writes into when the call will take the replayed route
@@ -702,7 +721,8 @@ class HierarchicalPatchModel(nn.Module):
         """models.py:498-537: average-pooled pyramid of the frame embedding + the frame itself, node-major."""
         B = int(num_samples_per_batch)
         conn = None
-        if self.use_connection_nodes and not self.use_main_graph_only:
+        mode = self._conn_rows_mode("frame")
+        if self.use_connection_nodes and not self.use_main_graph_only and not mode:
             conn = echo_frames.mean(dim=(2, 3)).unsqueeze(1).expand(B, self.num_aux_graphs + 1, C)
         sides = [] if self.use_main_graph_only else [2 ** g for g in range(1, self.num_aux_graphs + 1)]
         if sides and echo_frames.shape[1] == C and ops.pyramid_supported(echo_frames, sides) and os.environ.get("EG_POOL_PYRAMID", "1") != "0":
@@ -711,16 +731,17 @@ class HierarchicalPatchModel(nn.Module):
             # atomics per level (254 us each) -- 3.3 ms of a batch-1 training step whose GNN stack takes 1 ms
             n, n_conn = self._row_ranges()[:2]
             x = echo_frames.float()
-            feats = ops.pyramid_pack(x, sides, B, n, n_conn, out=self._static_node_feats(B, [x, conn]))
+            feats = ops.pyramid_pack(x, sides, B, n, n_conn, out=self._static_node_feats(B, [x, conn]), **mode)
             return self._finish_node_features(feats, B, node_coords, conn)
         maps = [F.adaptive_avg_pool2d(echo_frames, output_size=(p, p)) for p in sides]
         maps.append(echo_frames)
-        return self.pack_node_features(maps, B, node_coords, conn)
+        return self.pack_node_features(maps, B, node_coords, conn, **mode)
 
     def _finish_node_features(self, feats, B, node_coords, connection_embed):
-        """Connection-node rows and coordinate-node samples on top of the packed levels (models.py:524-533)."""
+        """Connection-node rows and coordinate-node samples on top of the packed levels (models.py:524-533).  connection_embed
+        None: the packing call has written the connection rows itself (``conn_rows=``)."""
         n, n_conn, _, main_base, coord_base = self._row_ranges()
-        if n_conn:
+        if n_conn and connection_embed is not None:
             feats = feats.clone() if feats.requires_grad else feats
             feats.view(B, n, C)[:, :n_conn, :] = connection_embed
         if self.use_coordinate_graph and not self.use_main_graph_only:
@@ -728,31 +749,35 @@ class HierarchicalPatchModel(nn.Module):
             feats = ops.scatter_coord_rows(feats, new, B, n, coord_base)
         return feats
 
-    def pack_node_features(self, level_maps, num_samples_per_batch: int, node_coords=None, connection_embed=None):
+    def pack_node_features(self, level_maps, num_samples_per_batch: int, node_coords=None, connection_embed=None,
+                           conn_rows: Optional[str] = None):
         """The tail every create_node_pixels variant of the reference shares (models.py:511-537, :603-636, :726-756):
         NCHW level maps (coarse to fine, the last one is the frame-sized map) -> [B*N, 128] in the GNN's node order,
         in one packing launch (eg_pack_levels) instead of a per-sample permute / cat loop.  The UNet / CNN variants
-        pass their own per-level feature maps and connection-node embeddings [B, naux+1, 128]."""
+        pass their own per-level feature maps and connection-node embeddings [B, naux+1, 128] -- or ``conn_rows`` ("level" /
+        "frame", ops.pack_levels) and no embeddings: the packing call then takes the means itself."""
         B = int(num_samples_per_batch)
         n, n_conn = self._row_ranges()[:2]
         maps = [m.float() for m in level_maps]
-        feats = ops.pack_levels(maps, B, n, n_conn, out=self._static_node_feats(B, maps + [connection_embed]))
+        feats = ops.pack_levels(maps, B, n, n_conn, out=self._static_node_feats(B, maps + [connection_embed]),
+                                **({"conn_rows": conn_rows} if conn_rows else {}))
         return self._finish_node_features(feats, B, node_coords, connection_embed)
 
     def pack_node_features_linear(self, features, linears, num_samples_per_batch: int, node_coords=None, connection_embed=None,
-                                  backward: str = "torch"):
+                                  backward: str = "torch", conn_rows: Optional[str] = None):
         """The UNet variant's whole tail (models.py:707-756): ``F.relu(self.linears[i](features[i]))`` for every level (1x1
         convolutions to 128 channels) AND the node-major packing in one launch (eg_conv1x1_relu_pack_levels); the 128-channel
         NCHW maps are never formed.  ``features``: decoder maps coarse to fine [B, C_l, p_l, p_l] (the last one frame-sized),
         ``linears``: the matching ``nn.Conv2d(C_l, 128, kernel_size=1)`` modules.  Connection-node embeddings
         [B, naux+1, 128] (means of the activated maps) come from the caller, as in ``pack_node_features``.  ``backward``: "torch" or
-        "hip" (ops.conv1x1_relu_pack_levels: the fixed-order HIP backward of the tail)."""
+        "hip" (ops.conv1x1_relu_pack_levels: the fixed-order HIP backward of the tail).  ``conn_rows`` as in ``pack_node_features``."""
         B = int(num_samples_per_batch)
         n, n_conn = self._row_ranges()[:2]
         fl = [f.float() for f in features]
         ws, bs = [m.weight for m in linears], [m.bias for m in linears]
         feats = ops.conv1x1_relu_pack_levels(fl, ws, bs, B, n, n_conn,
-                                             out=self._static_node_feats(B, fl + ws + bs + [connection_embed]), backward=backward)
+                                             out=self._static_node_feats(B, fl + ws + bs + [connection_embed]), backward=backward,
+                                             **({"conn_rows": conn_rows} if conn_rows else {}))
         return self._finish_node_features(feats, B, node_coords, connection_embed)
 
     def forward(self, data_batch=None, x=None, node_coords=None, edge_index=None, node_type=None, batch_idx=None):

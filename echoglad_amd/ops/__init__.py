@@ -22,4 +22,5 @@ from .frontend import adaptive_max_pool, adaptive_max_pool_train, conv3x3_relu_b
 from .embedder import embed_block, embed_block_train, pyramid_block, pyramid_block_train                                        # noqa: F401
 from .frame_prep import frame_prep                                                                                     # noqa: F401
 from .labels import node_labels                                                                                  # noqa: F401
-from .pack import avg_pool_pyramid, conv1x1_relu_pack_levels, pack_levels, pyramid_pack, pyramid_supported             # noqa: F401
+from .pack import (avg_pool_pyramid, conn_rows_bwd, conn_rows_chain, conn_rows_fwd, conn_rows_plan, conv1x1_relu_pack_levels,   # noqa: F401
+                   pack_levels, pyramid_pack, pyramid_supported)

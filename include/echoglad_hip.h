@@ -104,8 +104,9 @@ extern "C" {
  * 153: eg_conv1x1_relu_pack_bwd_workspace_bytes, eg_conv1x1_relu_pack_bwd_plan, eg_conv1x1_relu_pack_bwd.
  * 154: eg_conv1x1_relu_heads_fwd.
  * 155: eg_sgd_step, eg_rmsprop_step.
- * 156: eg_heatmap_render. */
-#define EG_ABI_VERSION 156
+ * 156: eg_heatmap_render.
+ * 157: eg_conn_rows_plan, eg_conn_rows_workspace_bytes, eg_conn_rows_fwd, eg_conn_rows_bwd. */
+#define EG_ABI_VERSION 157
 
 #define EG_CHANNELS 128 /* node_embedding_dim == node_hidden_dim (configs/default.yml:13-14) */
 
@@ -1030,6 +1031,42 @@ int eg_conv1x1_relu_heads_fwd(const float* const* level_feats, const float* cons
                               const float* const* level_biases, const int* level_channels, const int* level_side, int n_levels,
                               int batch, const float* w1, const float* s1, const float* t1, const float* w2, const float* s2,
                               const float* t2, const float* w3, const float* b3, int sigmoid, float* logits, eg_stream_t stream);
+
+/* ---- connection-node features: fixed-order column means over rows of the node array, in place (conn_rows.hip) --------------
+ * The reference gives every connection node (the first n_conn = naux + 1 rows of a frame, use_connection_nodes) the mean of a
+ * level's map (src/core/models.py:524-533, :737-752).  The values averaged are that level's packed node rows, so:
+ *   eg_conn_rows_fwd, for every frame b and connection row j < n_conn:
+ *     nodes[b * n_rows + j, c] = (sum_{i < src_rows[j]} nodes[b * n_rows + src_base[j] + i, c]) / (float)src_rows[j]
+ *   The level table (src_base[j], src_rows[j]) is free (HOST arrays of n_conn <= 16 entries): two rows may name the same source
+ *   -- it is summed once and stored to both, equal bits -- and sources that differ must be disjoint.  Rows >= n_conn are only
+ *   read; every row the call does not own keeps its bits.
+ * The order of summation is a function of a source's row count alone (eg_conn_rows_plan, host arithmetic, the one the launcher
+ *   uses): rows_per_chunk = max(128, ceil(rows / 512)), chunks = ceil(rows / rows_per_chunk) <= 512, the last chunk may be short
+ *   (50,176 rows: 392 chunks of 128).  One workgroup sums a chunk: row lane h = 0 .. 7 adds the chunk's rows h, h + 8, h + 16, ..
+ *   ascending, starting from 0; the 8 lane sums are added ascending.  A source of one chunk is divided and stored by that
+ *   workgroup.  Otherwise the chunk sums go to the workspace and a SECOND LAUNCH adds them ascending and divides.  Longest chain
+ *   of additions a value goes through: d(rows) = (ceil(min(rows, rows_per_chunk) / 8) - 1) + 7 + (chunks - 1); one division
+ *   behind it.  No atomics, no flags, no fences between workgroups.  The order does not depend on the batch, the grid, the device
+ *   or the other sources of the call: frame b's bits at batch B are its bits at batch 1.
+ * Workspace: batch * (sum over the DISTINCT sources of more than one chunk of chunks) * 512 bytes
+ *   (eg_conn_rows_workspace_bytes; 0 where the table is one eg_conn_rows_fwd refuses, and where no source has two chunks).
+ *   It may be NULL where that is 0.
+ *   eg_conn_rows_bwd, in place on d_nodes, for every distinct source range:
+ *     d_nodes[b, base + i, c] += t,  t = sum_{j: source j is that range, j ascending} d_nodes[b, j, c] * inv_j
+ *   with inv_j = 1.0f / (float)src_rows[j] taken in fp32 ON THE HOST; the first product starts t, each further term is a rounded
+ *   multiply, then a rounded add (never fused); the row then takes one rounded add.  One launch.  Rows in no source range, and the
+ *   connection rows of d_nodes themselves, keep their bits.
+ * Both: one or two launches on the caller's stream, no allocation, no synchronisation, no host read; capturable.  16-byte accesses,
+ *   a 512-B row per half-wave; row indices are 64-bit.
+ * Before any launch, EG_ERR_ARG: NULL pointers (the workspace where it is needed), n_conn / batch / n_rows < 1, src_rows < 1, a
+ *   source range that touches rows < n_conn or ends past n_rows, two sources that overlap without being equal, a node pointer
+ *   (or workspace) that is not 16-byte aligned; EG_ERR_UNSUPPORTED: n_conn > 16, batch * n_rows >= 2^31. */
+int eg_conn_rows_plan(int64_t rows, int* chunks, int* rows_per_chunk);
+size_t eg_conn_rows_workspace_bytes(const int64_t* src_base, const int64_t* src_rows, int n_conn, int batch, int64_t n_rows);
+int eg_conn_rows_fwd(float* nodes, int batch, int64_t n_rows, int n_conn, const int64_t* src_base, const int64_t* src_rows,
+                     void* workspace, eg_stream_t stream);
+int eg_conn_rows_bwd(float* d_nodes, int batch, int64_t n_rows, int n_conn, const int64_t* src_base, const int64_t* src_rows,
+                     eg_stream_t stream);
 
 /* ---- average-pool pyramid of the frame embedding: the head of create_node_pixels (src/core/models.py:511-521) -------------
  * eg_avg_pool_pyramid_fwd: level_maps[l] [planes, side_l, side_l] = F.adaptive_avg_pool2d(x [planes, frame, frame], side_l)
